@@ -16,6 +16,12 @@ PROMPT_LEN-token synthetic prompt generating GEN_TOKENS tokens
 
 Usage:  python bench.py --gpus N --steps K --warmup W
 (for N>1 the driver launches via torch.distributed.run, one rank/GPU)
+
+A plain run only sets up, warms up, times the K steps and prints the
+result line.  --dump-outputs DIR also writes the tokens the last timed
+step returned to DIR/outputs.npy (prompts are seeded per step, so two
+builds can be compared output for output).  --full adds the
+non-headline measurements (the Llama-3-70B TP rider at >=8 ranks).
 """
 
 import argparse
@@ -55,6 +61,12 @@ def main():
                              "accordingly and is reported)")
     parser.add_argument("--inflight", type=int, default=0,
                         help="concurrent events (default = replicas)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last "
+                             "timed step returned to DIR/<name>.npy")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the non-headline measurements "
+                             "(the Llama-3-70B TP rider on >=8 ranks)")
     args = parser.parse_args()
     inflight = args.inflight or args.replicas
 
@@ -94,13 +106,16 @@ def main():
 
     import random
 
-    random.seed(1234 + rank)
     vocab = 1000 if model_cfg == "tiny" else 120000
     prompt_len = args.prompt_len if on_gpu else 8
 
-    def make_body():
+    def make_body(index):
+        # one generator per event, seeded by the event's index: the steps
+        # run on pool threads, and a shared generator would hand its
+        # numbers out in whatever order the threads happen to interleave
+        rng = random.Random(1234 + rank + 7919 * index)
         return {
-            "inputs": [[random.randrange(1, vocab)
+            "inputs": [[rng.randrange(1, vocab)
                         for _ in range(prompt_len)] for _ in range(batch)],
             "max_tokens": args.gen_tokens,
         }
@@ -110,21 +125,28 @@ def main():
     import concurrent.futures
 
     pool = concurrent.futures.ThreadPoolExecutor(max_workers=inflight)
+    last_response = [None]
 
-    def one_step():
+    def one_step(index, keep=False):
         s0 = time.perf_counter()
-        server.test(path, body=make_body())
-        return (time.perf_counter() - s0) * 1000.0
+        resp = server.test(path, body=make_body(index))
+        took = (time.perf_counter() - s0) * 1000.0
+        if keep:
+            last_response[0] = resp
+        return took
 
     # warmup (includes weight init, first prefill, hipGraph capture)
-    list(pool.map(lambda _: one_step(), range(max(args.warmup, inflight))))
+    n_warm = max(args.warmup, inflight)
+    list(pool.map(one_step, range(n_warm)))
     if on_gpu:
         torch.cuda.synchronize()
     if dist:
         dist.barrier()
 
+    last = n_warm + args.steps - 1
     t0 = time.perf_counter()
-    latencies = list(pool.map(lambda _: one_step(), range(args.steps)))
+    latencies = list(pool.map(lambda i: one_step(i, keep=(i == last)),
+                              range(n_warm, n_warm + args.steps)))
     if on_gpu:
         torch.cuda.synchronize()
     if dist:
@@ -143,6 +165,9 @@ def main():
     reqs_per_sec = total_requests / elapsed
     latencies.sort()
     p50 = latencies[len(latencies) // 2]
+
+    if args.dump_outputs and last_response[0] is not None:
+        _dump_outputs(args.dump_outputs, last_response[0], rank)
 
     headline = None
     if rank == 0:
@@ -186,7 +211,7 @@ def main():
     # never lost.
     # only at the full-node run (world 8): at N=2/4 the rider would
     # eat the driver's scaling-sweep budget for a non-headline point
-    if dist and on_gpu and world_size >= 8 and \
+    if args.full and dist and on_gpu and world_size >= 8 and \
             os.environ.get("MLRUN_BENCH_TP", "1") != "0":
         import threading
 
@@ -212,6 +237,19 @@ def main():
 
     if dist:
         dist.destroy_process_group()
+
+
+def _dump_outputs(directory, response, rank=0):
+    """Write the generated tokens of one serving response, the
+    ``outputs`` a caller of the infer endpoint receives, as a
+    [batch, gen_tokens] float32 array (token ids are far below 2**24,
+    so float32 holds them exactly)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    name = "outputs.npy" if rank == 0 else f"outputs_rank{rank}.npy"
+    np.save(os.path.join(directory, name),
+            np.asarray(response["outputs"], dtype=np.float32))
 
 
 def _bench_tp70b(dist, rank, world_size, local_rank, steps=3, warmup=2,

@@ -461,7 +461,8 @@ class TestTorchCallbacks:
 class TestSignatureParity:
     """Lock in drop-in signature parity: every parameter of the
     reference's core entrypoints exists on ours (extra params are
-    allowed; the reference source is parsed textually)."""
+    allowed; the reference's parameter names are stored under
+    tests/golden/)."""
 
     CHECKS = [
         ("run.py", "new_function", None),
@@ -490,37 +491,20 @@ class TestSignatureParity:
         ("execution.py", "log_model",
          "mlrun_amd.execution.MLClientCtx"),
     ]
-    REF = "/root/reference/mlrun/"
+    GOLDEN = "golden/reference_signatures.json"
 
-    @staticmethod
-    def _ref_params(path, name, method):
+    @classmethod
+    def _ref_params(cls, path, name):
+        """Parameter names of the reference entrypoint, as recorded in
+        the stored fixture (names only; self/kwargs already removed)."""
+        import json
         import os
-        import re
 
-        ref_file = os.path.join("/root/reference/mlrun", path)
-        if not os.path.isfile(ref_file):
-            return None
-        src = open(ref_file).read()
-        pattern = (rf'\n    def {name}\(\s*self,?(.*?)\)( ->|:)'
-                   if method else rf'\ndef {name}\((.*?)\)( ->|:)')
-        match = re.search(pattern, src, re.S)
-        if not match:
-            return None
-        text = re.sub(r"\s+", " ", match.group(1))
-        out, depth, cur = set(), 0, ""
-        for ch in text + ",":
-            if ch in "([{":
-                depth += 1
-            if ch in ")]}":
-                depth -= 1
-            if ch == "," and depth == 0:
-                token = cur.split("=")[0].split(":")[0].strip().lstrip("*")
-                if token:
-                    out.add(token)
-                cur = ""
-            else:
-                cur += ch
-        return out - {"self", "", "kwargs", "class_args"}
+        golden = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                              cls.GOLDEN)
+        with open(golden) as f:
+            recorded = json.load(f)
+        return set(recorded[f"{path}::{name}"])
 
     def _ours(self, dotted, name):
         import importlib
@@ -545,9 +529,8 @@ class TestSignatureParity:
 
         failures = []
         for path, name, method in self.CHECKS + self.METHOD_CHECKS:
-            ref = self._ref_params(path, name, method)
-            if ref is None:
-                continue  # reference moved; skip silently
+            ref = self._ref_params(path, name)
+            assert ref, (path, name)  # every entrypoint is recorded
             ours = self._ours(method, name) | {"kwargs"}
             missing = ref - ours
             if missing:

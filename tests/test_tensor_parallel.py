@@ -162,7 +162,8 @@ class TestTpRiderPath:
                        LOCAL_RANK=str(rank))
             procs.append(subprocess.Popen(
                 [sys.executable, str(script)], env=env,
-                cwd=_os.getcwd(), stdout=subprocess.PIPE,
+                cwd=_os.path.dirname(_os.path.dirname(
+                    _os.path.abspath(__file__))), stdout=subprocess.PIPE,
                 stderr=subprocess.STDOUT))
         outs = [p.communicate(timeout=180)[0].decode() for p in procs]
         assert all(p.returncode == 0 for p in procs), outs
