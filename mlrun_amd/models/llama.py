@@ -685,6 +685,109 @@ class LlamaDecodeEngine:
             self.buf_tokens[slots] = self._select_tokens(logits)
         return logits
 
+    @torch.no_grad()
+    def prefill_packed(self, prompts, slots, starts=None) -> torch.Tensor:
+        """Varlen admission: prefill n prompts of ANY lengths in one
+        pass over their concatenated (packed) token stream.  Attention
+        is causal within each sequence only (``ops.attn_prefill``) and
+        K/V are written straight into cache rows ``slots``
+        (``ops.rope_kv_varlen``), so there is no padding and a
+        request's result does not depend on what it is packed with.
+
+        ``starts[i]`` (default 0) is the number of tokens already cached
+        in slot i: the chunk is written at positions starts[i].. and
+        attends to that prefix as well (prefix continuation).  Returns
+        last-token logits [n, vocab]; sets cache_lens and buf_tokens
+        for the slots like ``prefill_slots``.  bf16 KV caches only."""
+        cfg, w = self.cfg, self.weights
+        if self.kv_dtype == "fp8":
+            raise ValueError("packed prefill needs a bf16 KV cache")
+        prompts = [[int(t) for t in p] for p in prompts]
+        slot_list = [int(s) for s in slots]
+        n = len(prompts)
+        start_list = [0] * n if starts is None else \
+            [int(s) for s in starts]
+        if n == 0 or len(slot_list) != n or len(start_list) != n:
+            raise ValueError("prompts, slots and starts must be "
+                             "non-empty and of equal length")
+        if len(set(slot_list)) != n:
+            raise ValueError(f"duplicate slots in {slot_list}")
+        lens = [len(p) for p in prompts]
+        for prompt in prompts:
+            # checked on the host: an out-of-range id would make the
+            # embedding gather read outside the table on the device
+            if prompt and not 0 <= min(prompt) <= max(prompt) < \
+                    cfg.vocab_size:
+                raise ValueError(
+                    f"token id outside [0, {cfg.vocab_size}) in prompt")
+        for length, slot, start in zip(lens, slot_list, start_list):
+            if length < 1:
+                raise ValueError("every prompt needs at least one token")
+            if not 0 <= slot < self.B:
+                raise ValueError(f"slot {slot} outside [0, {self.B})")
+            if start < 0:
+                raise ValueError(f"negative start {start}")
+            if start + length >= cfg.max_seq_len:
+                raise ValueError(
+                    f"sequence of {start}+{length} tokens would reach "
+                    f"max_seq_len {cfg.max_seq_len}")
+        d = cfg.head_dim
+        T = sum(lens)
+        # one host->device copy for all the int32 index vectors
+        cu_list = [0]
+        pos_list, tok_slot_list = [], []
+        for length, slot, start in zip(lens, slot_list, start_list):
+            cu_list.append(cu_list[-1] + length)
+            pos_list.extend(range(start, start + length))
+            tok_slot_list.extend([slot] * length)
+        meta = torch.tensor(
+            pos_list + tok_slot_list + cu_list + slot_list + start_list,
+            dtype=torch.int32).to(self.device)
+        positions, tok_slot, cu_seqlens, slots_i32, kv_start = \
+            meta.split([T, T, n + 1, n, n])
+        tokens = torch.tensor([t for p in prompts for t in p],
+                              dtype=torch.int64).to(self.device)
+        max_q_len = max(lens)
+        x = w.embed[tokens]  # [T, H]
+        residual = x.contiguous()
+        hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
+                             eps=cfg.rms_eps)
+        for li, layer in enumerate(w.layers):
+            qkv = hidden @ layer["wqkv"].t()
+            ops.rope_kv_varlen(qkv, self.k_cache[li], self.v_cache[li],
+                               positions, tok_slot, self.cos_sin, w.hq)
+            q = qkv[:, :w.hq * d].view(T, w.hq, d)  # strided view
+            attn = ops.attn_prefill(q, self.k_cache[li], self.v_cache[li],
+                                    cu_seqlens, slots_i32, kv_start,
+                                    self.scale, max_q_len=max_q_len)
+            proj = attn @ layer["wo"].t()
+            self._maybe_allreduce(proj)
+            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
+                                           residual=residual,
+                                           eps=cfg.rms_eps)
+            gu = hidden @ layer["wgu"].t()
+            act = ops.swiglu_fused(gu.contiguous())
+            down = act @ layer["wdown"].t()
+            self._maybe_allreduce(down)
+            next_norm = w.layers[li + 1]["attn_norm"] \
+                if li + 1 < cfg.num_layers else w.final_norm
+            hidden = ops.fused_add_rmsnorm(down, next_norm,
+                                           residual=residual,
+                                           eps=cfg.rms_eps)
+        slots_long = slots_i32.long()
+        self.cache_lens[slots_long] = kv_start + (
+            cu_seqlens[1:] - cu_seqlens[:-1])
+        last = hidden[cu_seqlens[1:].long() - 1]
+        logits = last @ w.lm_head.t()
+        if self.per_slot_temp:
+            scores = logits.float() / self.buf_temp[slots_long]
+            u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
+            self.buf_tokens[slots_long] = (
+                scores - torch.log(-torch.log(u))).argmax(dim=-1)
+        else:
+            self.buf_tokens[slots_long] = self._select_tokens(logits)
+        return logits
+
     # -------------------------------------------------------- generate
     @torch.no_grad()
     def generate(self, tokens: torch.Tensor, max_new_tokens: int = 32
@@ -726,6 +829,9 @@ class LlamaServer:
       the engine batch size
     - ``batch_window_ms``: small concurrent requests coalesce into one
       engine pass (dynamic batching)
+    - ``prefill``: how continuous scheduling prefills an admitted
+      group — "exact" (default) one pass per distinct prompt length,
+      "packed" one varlen pass over all of them (bf16 KV only)
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -734,7 +840,7 @@ class LlamaServer:
                  replicas=1, weight_dtype="bf16", kv_dtype="bf16",
                  scheduling="batch", stop_token: int = None,
                  temperature: float = 0.0, top_k: int = 0,
-                 **class_args):
+                 prefill: str = "exact", **class_args):
         import queue as queue_mod
         import threading
 
@@ -757,6 +863,13 @@ class LlamaServer:
         self.weight_dtype = weight_dtype
         self.kv_dtype = kv_dtype
         self.scheduling = scheduling  # "batch" | "continuous"
+        # continuous admission: "exact" = one prefill_slots pass per
+        # distinct prompt length; "packed" = one prefill_packed pass
+        # over the whole mixed-length group (bf16 KV only)
+        if prefill not in ("exact", "packed"):
+            raise ValueError(f"unknown prefill mode {prefill!r} "
+                             "(expected 'exact' or 'packed')")
+        self.prefill = prefill
         self.stop_token = stop_token  # finish a request at this token
         self.temperature = float(temperature)
         self.top_k = int(top_k)
@@ -805,6 +918,11 @@ class LlamaServer:
         import threading
 
         cfg = self._build_config()
+        if self.prefill == "packed" and self.kv_dtype == "fp8":
+            raise ValueError(
+                'prefill="packed" needs a bf16 KV cache (the packed '
+                'attention kernel does not read fp8 caches): use '
+                'kv_dtype="bf16" or prefill="exact"')
         if not torch.cuda.is_available():
             self.replicas = 1
         first = LlamaDecodeEngine(cfg, self.batch_size, device=self.device,
@@ -1007,6 +1125,17 @@ class LlamaServer:
                     by_len.setdefault(len(prompt), []).append(
                         (prompt, slot))
                 try:
+                    if self.prefill == "packed":
+                        # the whole mixed-length group in ONE pass:
+                        # packed rows carry no padding, so the result
+                        # is independent of co-arriving traffic too
+                        by_len = {}
+                        slot_ids = torch.tensor(admit_slots,
+                                                dtype=torch.long)
+                        with stream_ctx():
+                            engine.prefill_packed(prompts, admit_slots)
+                            out_ring[slot_ids, step % ring_len] = \
+                                engine.buf_tokens[slot_ids]
                     for length, group in by_len.items():
                         tokens = torch.tensor(
                             [p for p, _ in group], dtype=torch.int64)

@@ -443,6 +443,81 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor,
     return out
 
 
+# -------------------------------------------------------- packed prefill
+
+
+def rope_kv_varlen(qkv: torch.Tensor, k_cache: torch.Tensor,
+                   v_cache: torch.Tensor, positions: torch.Tensor,
+                   tok_slot: torch.Tensor, cos_sin: torch.Tensor, hq: int):
+    """Packed-prefill rope(q,k) + KV append.  qkv [T, (hq+2*hkv)*d] is
+    the packed projection buffer of several sequences; token t is roped
+    in place at positions[t] and its k/v land in
+    cache[tok_slot[t], :, positions[t]].  bf16 caches only."""
+    T = qkv.shape[0]
+    hkv, d = k_cache.shape[1], k_cache.shape[3]
+    if qkv.is_cuda:
+        _require_hip().rope_kv_varlen(qkv, k_cache, v_cache, positions,
+                                      tok_slot, cos_sin, hq)
+        return
+    q = qkv[:, :hq * d].view(T, hq, d)
+    k = qkv[:, hq * d:(hq + hkv) * d].view(T, hkv, d)
+    v = qkv[:, (hq + hkv) * d:(hq + 2 * hkv) * d].view(T, hkv, d)
+    rope_inplace(q, positions, cos_sin)
+    rope_inplace(k, positions, cos_sin)
+    for t in range(T):
+        slot, pos = int(tok_slot[t]), int(positions[t])
+        k_cache[slot, :, pos] = k[t]
+        v_cache[slot, :, pos] = v[t]
+
+
+def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor,
+                 v_cache: torch.Tensor, cu_seqlens: torch.Tensor,
+                 slots: torch.Tensor, kv_start: torch.Tensor,
+                 scale: float = None, out: torch.Tensor = None,
+                 max_q_len: int = None) -> torch.Tensor:
+    """Packed (varlen) causal GQA prefill attention over the KV cache.
+
+    q [T, Hq, D] holds n sequences back to back: sequence i owns rows
+    cu_seqlens[i]..cu_seqlens[i+1].  Its query j sits at position
+    p = kv_start[i] + j and attends to rows 0..p of
+    cache[slots[i], h // G] — the chunk's own k/v must already be in
+    the cache (rope_kv_varlen).  Returns out [T, Hq*D] bf16.
+    max_q_len (the longest chunk) sizes the GPU grid; pass it from the
+    host-side lengths to avoid a device sync."""
+    T, Hq, D = q.shape
+    Hkv = k_cache.shape[1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty(T, Hq * D, dtype=q.dtype, device=q.device)
+    if q.is_cuda:
+        ops = _require_hip()
+        if max_q_len is None:
+            cu = cu_seqlens.tolist()
+            max_q_len = max((b - a for a, b in zip(cu, cu[1:])), default=0)
+        ops.attn_prefill(out, q, k_cache, v_cache, cu_seqlens, slots,
+                         kv_start, scale, int(max_q_len))
+        return out
+    # fp32 reference: one query row at a time, the same expressions as
+    # the attn_decode reference (so a length-1 chunk matches it bit
+    # for bit)
+    G = Hq // Hkv
+    cu = cu_seqlens.tolist()
+    out_v = out.view(T, Hq, D)
+    for i in range(len(cu) - 1):
+        slot, start = int(slots[i]), int(kv_start[i])
+        for j in range(cu[i + 1] - cu[i]):
+            row = cu[i] + j
+            length = start + j + 1
+            for h in range(Hq):
+                kvh = h // G
+                qv = q[row, h].float()
+                keys = k_cache[slot, kvh, :length].float()
+                vals = v_cache[slot, kvh, :length].float()
+                scores = torch.softmax(keys @ qv * scale, dim=0)
+                out_v[row, h] = (scores @ vals).to(q.dtype)
+    return out
+
+
 def kv_append(k_cache, v_cache, k_new, v_new, positions):
     """Scatter the new token K/V into the cache at positions[b]."""
     if k_cache.is_cuda:

@@ -337,6 +337,77 @@ void kv_append(torch::Tensor kc, torch::Tensor vc, torch::Tensor knew,
                    src_stride, stream());
 }
 
+// packed prefill: rope(q,k) in place + KV append at
+// cache[tok_slot[t], :, positions[t]] for every packed token t
+void rope_kv_varlen(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc,
+                    torch::Tensor positions, torch::Tensor tok_slot,
+                    torch::Tensor cos_sin, int64_t hq) {
+  CHECK_DEV(qkv); CHECK_CONTIG(qkv); CHECK_BF16(qkv);
+  CHECK_DEV(kc); CHECK_CONTIG(kc); CHECK_BF16(kc);
+  CHECK_DEV(vc); CHECK_CONTIG(vc); CHECK_BF16(vc);
+  CHECK_DEV(positions); CHECK_CONTIG(positions); CHECK_I32(positions);
+  CHECK_DEV(tok_slot); CHECK_CONTIG(tok_slot); CHECK_I32(tok_slot);
+  CHECK_DEV(cos_sin); CHECK_CONTIG(cos_sin); CHECK_F32(cos_sin);
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes(),
+              "caches must be [B, Hkv, Smax, D] of equal shape");
+  int B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [T, rows]");
+  int64_t T = qkv.size(0);
+  TORCH_CHECK(hq >= 1 && qkv.size(1) >= (hq + 2 * Hkv) * D,
+              "qkv row too small");
+  TORCH_CHECK(D % 2 == 0 && D / 2 <= 1024, "bad head dim");
+  TORCH_CHECK(positions.numel() == T && tok_slot.numel() == T,
+              "positions/tok_slot must hold one entry per token");
+  TORCH_CHECK(cos_sin.dim() == 3 && cos_sin.size(1) == D / 2 &&
+              cos_sin.size(2) == 2, "cos_sin must be [max_pos, D/2, 2]");
+  TORCH_CHECK(hq + 2 * Hkv <= 65535, "too many heads");
+  if (T == 0) return;
+  launch_rope_kv_varlen(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                        positions.data_ptr(), tok_slot.data_ptr(),
+                        cos_sin.data_ptr(), (int)T, B, (int)hq, Hkv, Smax, D,
+                        (int)cos_sin.size(0), qkv.size(1), stream());
+}
+
+// packed prefill: causal GQA flash attention over the slot-indexed cache
+void attn_prefill(torch::Tensor o, torch::Tensor q, torch::Tensor kc,
+                  torch::Tensor vc, torch::Tensor cu_seqlens,
+                  torch::Tensor slots, torch::Tensor kv_start, double scale,
+                  int64_t max_q_len) {
+  CHECK_DEV(o); CHECK_CONTIG(o); CHECK_BF16(o);
+  CHECK_DEV(q); CHECK_BF16(q);
+  CHECK_DEV(kc); CHECK_CONTIG(kc); CHECK_BF16(kc);
+  CHECK_DEV(vc); CHECK_CONTIG(vc); CHECK_BF16(vc);
+  CHECK_DEV(cu_seqlens); CHECK_CONTIG(cu_seqlens); CHECK_I32(cu_seqlens);
+  CHECK_DEV(slots); CHECK_CONTIG(slots); CHECK_I32(slots);
+  CHECK_DEV(kv_start); CHECK_CONTIG(kv_start); CHECK_I32(kv_start);
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes(),
+              "caches must be [B, Hkv, Smax, D] of equal shape");
+  long long q_row_stride = check_head_view(q);
+  int64_t T = q.size(0);
+  int Hq = q.size(1), D = q.size(2);
+  int B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2);
+  TORCH_CHECK(D == 128 && kc.size(3) == D,
+              "attn_prefill requires head_dim 128");
+  TORCH_CHECK(Hq % Hkv == 0 && Hq / Hkv <= 8,
+              "grouped heads per kv head must divide and be <= 8");
+  TORCH_CHECK(o.numel() == T * Hq * D, "out must be [T, Hq*D]");
+  // the kernel reads q and the caches with 16 B vector loads
+  TORCH_CHECK(q_row_stride % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q rows must be 16-byte aligned");
+  int64_t nseq = slots.numel();
+  TORCH_CHECK(cu_seqlens.numel() == nseq + 1 && kv_start.numel() == nseq,
+              "cu_seqlens [n+1], slots [n], kv_start [n]");
+  TORCH_CHECK(nseq <= 65535 && Hq <= 65535, "grid too large");
+  TORCH_CHECK(max_q_len >= 0 && max_q_len <= T, "bad max_q_len");
+  if (T == 0 || nseq == 0 || max_q_len == 0) return;
+  launch_attn_prefill(o.data_ptr(), q.data_ptr(), kc.data_ptr(),
+                      vc.data_ptr(), cu_seqlens.data_ptr(),
+                      slots.data_ptr(), kv_start.data_ptr(), (int)T,
+                      (int)nseq, B, Hq, Hkv, Smax, (float)scale,
+                      q_row_stride, (int)max_q_len, stream());
+}
+
 void softmax(torch::Tensor out, torch::Tensor in) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(in); CHECK_CONTIG(in); CHECK_BF16(in);
@@ -479,6 +550,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_scale") = py::none(),
         "GQA decode attention (bf16 or fp8 KV cache)");
   m.def("kv_append", &kv_append, "append token K/V into cache");
+  m.def("rope_kv_varlen", &rope_kv_varlen, py::arg("qkv"), py::arg("kc"),
+        py::arg("vc"), py::arg("positions"), py::arg("tok_slot"),
+        py::arg("cos_sin"), py::arg("hq"),
+        "packed-prefill rope(q,k) + KV append by per-token slot");
+  m.def("attn_prefill", &attn_prefill, py::arg("o"), py::arg("q"),
+        py::arg("kc"), py::arg("vc"), py::arg("cu_seqlens"),
+        py::arg("slots"), py::arg("kv_start"), py::arg("scale"),
+        py::arg("max_q_len"),
+        "packed causal GQA flash-attention prefill over the KV cache");
   m.def("softmax", &softmax, "row softmax (bf16)");
   m.def("tree_ensemble", &tree_ensemble, "GBDT ensemble inference (f32)");
   m.def("window_ingest", &window_ingest,

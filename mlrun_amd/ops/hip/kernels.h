@@ -79,6 +79,19 @@ void launch_kv_append(void* Kc, void* Vc, const void* knew, const void* vnew,
                       const void* positions, int B, int Hkv, int Smax, int D,
                       long long src_row_stride, void* stream);
 
+void launch_rope_kv_varlen(void* qkv, void* Kc, void* Vc,
+                           const void* positions, const void* tok_slot,
+                           const void* cos_sin, int T, int B, int Hq,
+                           int Hkv, int Smax, int D, int max_pos,
+                           long long row_stride, void* stream);
+
+void launch_attn_prefill(void* O, const void* Q, const void* Kc,
+                         const void* Vc, const void* cu_seqlens,
+                         const void* slots, const void* kv_start, int T,
+                         int nseq, int B, int Hq, int Hkv, int Smax,
+                         float scale, long long q_row_stride,
+                         int max_q_len, void* stream);
+
 void launch_softmax(void* out, const void* in, int rows, int cols,
                     void* stream);
 

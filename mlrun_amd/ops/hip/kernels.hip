@@ -1809,6 +1809,331 @@ void launch_kv_append(void* Kc, void* Vc, const void* knew, const void* vnew,
 }
 
 // ---------------------------------------------------------------------
+// Packed (varlen) prefill, part 1: RoPE + KV append over a packed token
+// stream.  Same math as rope_kv_fused_kernel; the only difference is
+// that token t's cache row is tok_slot[t] rather than the row index,
+// so tokens of several sequences share one launch.  bf16 caches only.
+// grid: (T, Hq + 2*Hkv); block: D/2 threads.
+// A token whose slot or position is out of range is left untouched.
+// ---------------------------------------------------------------------
+__global__ void rope_kv_varlen_kernel(
+    unsigned short* __restrict__ qkv, unsigned short* __restrict__ Kc,
+    unsigned short* __restrict__ Vc, const int* __restrict__ positions,
+    const int* __restrict__ tok_slot, const float* __restrict__ cos_sin,
+    int B, int Hq, int Hkv, int Smax, int D, int max_pos,
+    long long row_stride) {
+  const int t = blockIdx.x;
+  const int y = blockIdx.y;
+  const int i = threadIdx.x;  // 0..D/2-1
+  const int half = D >> 1;
+  const int pos = positions[t];
+  const int slot = tok_slot[t];
+  if (pos < 0 || pos >= max_pos || pos >= Smax ||
+      (unsigned)slot >= (unsigned)B)
+    return;
+  unsigned short* row = qkv + (size_t)t * row_stride;
+  if (y < Hq + Hkv) {
+    unsigned short* head = row + (size_t)y * D;
+    const float c = cos_sin[((size_t)pos * half + i) * 2];
+    const float s = cos_sin[((size_t)pos * half + i) * 2 + 1];
+    const float a = bf2f(head[i]);
+    const float bvf = bf2f(head[i + half]);
+    const unsigned short lo = f2bf(a * c - bvf * s);
+    const unsigned short hi = f2bf(bvf * c + a * s);
+    head[i] = lo;
+    head[i + half] = hi;
+    if (y >= Hq) {
+      const int kvh = y - Hq;
+      unsigned short* dst = Kc +
+          (((size_t)slot * Hkv + kvh) * Smax + pos) * D;
+      dst[i] = lo;
+      dst[i + half] = hi;
+    }
+  } else {
+    const int kvh = y - Hq - Hkv;
+    const unsigned short* src = row + (size_t)(Hq + Hkv + kvh) * D;
+    unsigned short* dst =
+        Vc + (((size_t)slot * Hkv + kvh) * Smax + pos) * D;
+    dst[i] = src[i];
+    dst[i + half] = src[i + half];
+  }
+}
+
+void launch_rope_kv_varlen(void* qkv, void* Kc, void* Vc,
+                           const void* positions, const void* tok_slot,
+                           const void* cos_sin, int T, int B, int Hq,
+                           int Hkv, int Smax, int D, int max_pos,
+                           long long row_stride, void* stream) {
+  hipLaunchKernelGGL(rope_kv_varlen_kernel, dim3(T, Hq + 2 * Hkv),
+                     dim3(D / 2), 0, (hipStream_t)stream,
+                     (unsigned short*)qkv, (unsigned short*)Kc,
+                     (unsigned short*)Vc, (const int*)positions,
+                     (const int*)tok_slot, (const float*)cos_sin, B, Hq,
+                     Hkv, Smax, D, max_pos, row_stride);
+}
+
+// ---------------------------------------------------------------------
+// Packed (varlen) prefill, part 2: causal GQA flash-attention forward
+// over the slot-indexed KV cache.
+//
+//   query j of sequence i sits at position p = kv_start[i] + j and
+//   attends to rows 0..p of cache[slots[i], h / G].
+//
+// grid (ceil(max_q_len / 64), Hq, n); block 256 = 4 waves.  A workgroup
+// owns 64 query rows of one (sequence, q-head); each wave owns 16 rows,
+// one MFMA M-tile.  KV is walked in 64-row tiles up to the workgroup's
+// last query position only; tiles above the diagonal are never visited,
+// and a wave skips the MFMAs of a tile that lies wholly above its own
+// 16 rows.  Only tiles that reach past a wave's first row apply the
+// element mask.
+//
+// Both products run TRANSPOSED on v_mfma_f32_16x16x32_bf16:
+//   S^T = K . Q^T   A = K rows from LDS (one 16 B row read per lane),
+//                   B = the Q fragments, loaded once, kept in registers
+//   O^T += V^T . P^T
+// The transposed score tile has its query on the lane (col = lane & 15)
+// and its keys in the registers (row = 4*(lane >> 4) + reg), which is
+// already the B-operand shape of the second product once a lane's
+// registers of two 16-key tiles are packed to 8 bf16: P never leaves
+// the registers, so there is no LDS round trip for it.  The k order
+// inside such a 32-key step is permuted (slot 8h+j = key 16*(j>>2) +
+// 4h + (j&3)); the V^T operand is read in the same order by two
+// ds_read_b64_tr_b16 per fragment, which transpose a 4-key x 16-dim
+// block of the row-major V tile on the way out of LDS, so V is staged
+// exactly as it lies in the cache (no transposed stage, no 2-byte
+// scatter writes).  With the query on the lane, the softmax row max
+// and sum are a register reduction plus two cross-lane steps (the 4
+// lanes lane&15, +16, +32, +48 share a row) and the rescale factor is
+// a per-lane scalar.
+//
+// K/V tiles are fetched with 16 B global loads into registers while the
+// previous tile is being consumed and written to LDS after the barrier
+// (rows padded, like the decode kernel's ATTN_LDS_PAD).  Cache rows at
+// or past the sequence's end are never loaded: they are staged as
+// zeros, so stale Inf/NaN in the cache cannot reach either MFMA.
+// ---------------------------------------------------------------------
+#define PF_BM 64
+#define PF_BN 64
+// LDS row = 128 halves + 16 of padding (288 B): consecutive rows start
+// 8 banks apart, which makes both the 16 B K row reads and the 8 B
+// transposed V reads conflict-free within their lane groups.
+#define PF_ROW (128 + 16)
+
+typedef __attribute__((ext_vector_type(4))) short short4v;
+
+DEV short4v pf_read_tr16(const unsigned short* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) short4v*)p);
+}
+
+// f32 -> bf16, round-to-nearest-even like f2bf, but through the
+// compiler's conversion so that gfx950's packed hardware convert is
+// used (16 of these per KV tile sit between the two MFMA blocks)
+DEV short pf_f2bf(float f) {
+  return __builtin_bit_cast(short, (__bf16)f);
+}
+
+__global__ __launch_bounds__(256) void attn_prefill_kernel(
+    unsigned short* __restrict__ O, const unsigned short* __restrict__ Q,
+    const unsigned short* __restrict__ Kc,
+    const unsigned short* __restrict__ Vc,
+    const int* __restrict__ cu_seqlens, const int* __restrict__ slots,
+    const int* __restrict__ kv_start, int T, int B, int Hq, int Hkv,
+    int Smax, float scale_log2e, long long q_row_stride) {
+  constexpr int D = 128;
+  __shared__ __attribute__((aligned(16)))
+      unsigned short lds[2 * PF_BN * PF_ROW];
+  unsigned short* kbuf = lds;
+  unsigned short* vbuf = lds + PF_BN * PF_ROW;
+
+  const int seq = blockIdx.z;
+  const int h = blockIdx.y;
+  const int q0 = blockIdx.x * PF_BM;
+  // --- block-uniform setup and early exits (before any barrier)
+  const int row0 = cu_seqlens[seq];
+  int qlen = cu_seqlens[seq + 1] - row0;
+  if (row0 < 0) return;
+  qlen = min(qlen, T - row0);
+  if (q0 >= qlen) return;  // tile past this sequence's end
+  const int slot = slots[seq];
+  const int start = kv_start[seq];
+  if ((unsigned)slot >= (unsigned)B || start < 0) return;
+  const int q_hi = min(q0 + PF_BM, qlen);      // one past the last row
+  const int kv_end = min(start + q_hi, Smax);  // keys this block sees
+  const int ntiles = (kv_end + PF_BN - 1) / PF_BN;
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int lq = lane & 15;  // query column of the transposed tiles
+  const int lh = lane >> 4;
+  const int wrow0 = q0 + wave * 16;
+  const bool wave_active = wrow0 < qlen;
+  const int qr = wrow0 + lq;
+  const bool row_valid = qr < qlen;
+  const int pos = start + qr;                       // this lane's query
+  const int wave_min_pos = start + wrow0;
+  const int wave_max_pos = start + min(wrow0 + 15, qlen - 1);
+
+  // --- Q fragments: loaded once, live across the whole tile loop
+  short8v qf[4];
+  {
+    const unsigned short* qp =
+        Q + (size_t)(row0 + min(qr, qlen - 1)) * q_row_stride +
+        (size_t)h * D + lh * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      qf[ks] = *reinterpret_cast<const short8v*>(qp + ks * 32);
+  }
+
+  const int kvh = h / (Hq / Hkv);
+  const size_t cbase = ((size_t)slot * Hkv + kvh) * Smax * D;
+  const unsigned short* kbase = Kc + cbase;
+  const unsigned short* vbase = Vc + cbase;
+
+  // staging: 64 rows x 16 chunks of 16 B = 4 chunks per thread
+  short8v kreg[4], vreg[4];
+  auto issue = [&](int tile0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      const int key = tile0 + (c >> 4);
+      const short8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
+      kreg[i] = zero;
+      vreg[i] = zero;
+      if (key < kv_end) {
+        const size_t off = (size_t)key * D + (c & 15) * 8;
+        kreg[i] = *reinterpret_cast<const short8v*>(kbase + off);
+        vreg[i] = *reinterpret_cast<const short8v*>(vbase + off);
+      }
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      const int off = (c >> 4) * PF_ROW + (c & 15) * 8;
+      *reinterpret_cast<short8v*>(kbuf + off) = kreg[i];
+      *reinterpret_cast<short8v*>(vbuf + off) = vreg[i];
+    }
+  };
+
+  f32x4v o[8];
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) o[dt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  float m = -1e30f;  // running row max (log2 domain), finite on purpose
+  float l = 0.f;     // this lane's share of the row sum
+
+  issue(0);
+  for (int t = 0; t < ntiles; ++t) {
+    const int tile0 = t * PF_BN;
+    __syncthreads();  // everyone is done reading the previous tile
+    commit();
+    __syncthreads();
+    if (t + 1 < ntiles) issue(tile0 + PF_BN);  // flies under the MFMAs
+    if (!wave_active || tile0 > wave_max_pos) continue;
+
+    // --- S^T = K . Q^T : 4 key tiles x 4 k-steps
+    f32x4v s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      s[kt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      const unsigned short* kp = kbuf + (kt * 16 + lq) * PF_ROW + lh * 8;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const short8v kf = *reinterpret_cast<const short8v*>(kp + ks * 32);
+        s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[kt],
+                                                        0, 0, 0);
+      }
+    }
+    // --- scale, causal mask on diagonal tiles only, tile max
+    const bool need_mask = tile0 + PF_BN - 1 > wave_min_pos;
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = s[kt][r] * scale_log2e;
+        if (need_mask && tile0 + kt * 16 + lh * 4 + r > pos)
+          x = -__builtin_inff();
+        s[kt][r] = x;
+        mx = fmaxf(mx, x);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    // --- online softmax: rescale everything held at the old max
+    const float m_new = fmaxf(m, mx);
+    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+    m = m_new;
+    float psum = 0.f;
+    short8v pb[2];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_new);
+        psum += p;
+        pb[kt >> 1][(kt & 1) * 4 + r] = pf_f2bf(p);
+      }
+    }
+    l = l * alpha + psum;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
+    // --- O^T += V^T . P^T : 8 dim tiles x 2 k-steps of 32 keys
+    const unsigned short* vp =
+        vbuf + (lh * 4 + (lq >> 2)) * PF_ROW + (lq & 3) * 4;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const short4v lo = pf_read_tr16(vp + (ks * 32) * PF_ROW + dt * 16);
+        const short4v hi =
+            pf_read_tr16(vp + (ks * 32 + 16) * PF_ROW + dt * 16);
+        const short8v vf =
+            __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks], o[dt],
+                                                        0, 0, 0);
+      }
+    }
+  }
+
+  // --- epilogue: finish the row sum across the 4 lanes of a row
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (!row_valid) return;
+  const float inv = 1.f / l;
+  unsigned short* op =
+      O + ((size_t)(row0 + qr) * Hq + h) * D + lh * 4;
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) {
+    ushort4 w;
+    w.x = f2bf(o[dt][0] * inv);
+    w.y = f2bf(o[dt][1] * inv);
+    w.z = f2bf(o[dt][2] * inv);
+    w.w = f2bf(o[dt][3] * inv);
+    *reinterpret_cast<ushort4*>(op + dt * 16) = w;
+  }
+}
+
+void launch_attn_prefill(void* O, const void* Q, const void* Kc,
+                         const void* Vc, const void* cu_seqlens,
+                         const void* slots, const void* kv_start, int T,
+                         int nseq, int B, int Hq, int Hkv, int Smax,
+                         float scale, long long q_row_stride,
+                         int max_q_len, void* stream) {
+  const int qtiles = (max_q_len + PF_BM - 1) / PF_BM;
+  if (qtiles <= 0 || nseq <= 0) return;
+  hipLaunchKernelGGL(attn_prefill_kernel, dim3(qtiles, Hq, nseq),
+                     dim3(256), 0, (hipStream_t)stream,
+                     (unsigned short*)O, (const unsigned short*)Q,
+                     (const unsigned short*)Kc, (const unsigned short*)Vc,
+                     (const int*)cu_seqlens, (const int*)slots,
+                     (const int*)kv_start, T, B, Hq, Hkv, Smax,
+                     scale * 1.4426950408889634f, q_row_stride);
+}
+
+// ---------------------------------------------------------------------
 // Row softmax (bf16 in/out, online single pass over LDS-staged row,
 // used by classic-model servers & tests)
 // ---------------------------------------------------------------------
