@@ -276,6 +276,8 @@ class LlamaDecodeEngine:
             device=self.device) if self.on_gpu else None
         self._graph = None
         self._ksplits = {}
+        # speculative decoding (opt-in): running acceptance counters
+        self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
 
     # ------------------------------------------------------------ gemm
     def _plan(self, w_):
@@ -807,6 +809,211 @@ class LlamaDecodeEngine:
             generated.append(self.buf_tokens.clone())
         return torch.stack(generated, dim=1)
 
+    # ----------------------------------------------------- speculative
+    def _check_speculative(self, k: int):
+        """Host-side preconditions of the verify path (no device work)."""
+        if self.temperature > 0.0 or self.per_slot_temp:
+            raise ValueError(
+                "speculative decoding is greedy only (temperature "
+                f"{self.temperature} samples)")
+        if self.kv_dtype != "bf16":
+            raise ValueError("speculative decoding needs a bf16 KV cache "
+                             f"(kv_dtype={self.kv_dtype!r})")
+        if self.weight_dtype != "bf16":
+            raise ValueError("speculative decoding needs bf16 weights "
+                             f"(weight_dtype={self.weight_dtype!r})")
+        if self.tp_size != 1:
+            raise ValueError("speculative decoding needs tp_size == 1")
+        if not 1 <= int(k) <= ops.VERIFY_MAX_QL - 1:
+            raise ValueError(
+                f"speculative k must be in [1, {ops.VERIFY_MAX_QL - 1}], "
+                f"got {k}")
+
+    def _verify_gemm(self, a, w_, QL):
+        """a [B*QL, K] @ w_[N, K]^T for the verify pass: the library
+        GEMM on the GPU (B * QL rows is past the skinny kernel's range).
+        The CPU reference runs decode_step's fp32 reference GEMM once
+        per query offset j on the B rows (b, j): a CPU GEMM's summation
+        order depends on its row count, and only the same call on the
+        same shape rounds every row like decode_step does, which is
+        what lets the CPU tier compare the two paths token for token."""
+        if self.on_gpu:
+            return a @ w_.t()
+        out = torch.empty(a.shape[0], w_.shape[0], dtype=a.dtype)
+        for j in range(QL):
+            out[j::QL] = ops.skinny_gemm(a[j::QL].contiguous(), w_)
+        return out
+
+    @torch.no_grad()
+    def verify_step(self, drafts: torch.Tensor):
+        """One speculative step: score the pending token plus k drafted
+        tokens per sequence in ONE pass over the weights and accept the
+        longest draft prefix that greedy decoding would have produced.
+
+        drafts [B, k] (1 <= k <= 7) on the engine's device.  Row (b, j)
+        of the pass carries buf_tokens[b] (j = 0) or drafts[b, j-1] at
+        position cache_lens[b] + j.  Returns (pred [B, k+1],
+        n_accepted [B]) as device tensors, without a host sync:
+        pred[b, j] is the greedy token after row (b, j), n_accepted[b]
+        the number of leading drafts equal to pred.  Then cache_lens[b]
+        advances by n_accepted[b] + 1 and buf_tokens[b] becomes
+        pred[b, n_accepted[b]], exactly the state n_accepted[b] + 1
+        decode steps leave behind.  K/V rows of rejected drafts stay
+        beyond cache_lens: never read, overwritten later.  All logits
+        are kept in buf_verify_logits [B, k+1, vocab]."""
+        cfg, w = self.cfg, self.weights
+        if drafts.dim() != 2 or drafts.shape[0] != self.B:
+            raise ValueError(f"drafts must be [{self.B}, k], got "
+                             f"{tuple(drafts.shape)}")
+        k = drafts.shape[1]
+        self._check_speculative(k)
+        B, QL, d = self.B, k + 1, cfg.head_dim
+        T = B * QL
+        drafts = drafts.to(device=self.device, dtype=torch.int64)
+        # an out-of-range id would make the embedding gather read
+        # outside the table; clamped it is merely a wrong guess (the
+        # acceptance below compares the ORIGINAL ids, so it is rejected)
+        fed = drafts.clamp(0, cfg.vocab_size - 1)
+        tokens = torch.cat([self.buf_tokens.view(B, 1), fed], dim=1)
+        # idle slots park at the cache end, like decode_step
+        base = torch.clamp(self.cache_lens, min=0,
+                           max=cfg.max_seq_len - QL)
+        steps = torch.arange(QL, dtype=torch.int32, device=self.device)
+        positions = (base.view(B, 1) + steps).reshape(T)
+        tok_slot = torch.arange(B, dtype=torch.int32, device=self.device
+                                ).repeat_interleave(QL)
+        nsplit, ws = None, None
+        if self.on_gpu:
+            nsplit = ops.pick_verify_nsplit(B, w.hkv, cfg.max_seq_len)
+            need = ops.attn_verify_ws_numel(B, QL, w.hq, nsplit)
+            ws = getattr(self, "_verify_ws", None)
+            if nsplit > 1 and (ws is None or ws.numel() < need):
+                ws = self._verify_ws = torch.empty(
+                    need, dtype=torch.float32, device=self.device)
+        residual = w.embed[tokens.reshape(T)].contiguous()
+        hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
+                             eps=cfg.rms_eps)
+        for li, layer in enumerate(w.layers):
+            qkv = self._verify_gemm(hidden, layer["wqkv"], QL)
+            ops.rope_kv_varlen(qkv, self.k_cache[li], self.v_cache[li],
+                               positions, tok_slot, self.cos_sin, w.hq)
+            q = qkv[:, :w.hq * d].view(B, QL, w.hq, d)  # strided view
+            attn = ops.attn_verify(q, self.k_cache[li], self.v_cache[li],
+                                   base, self.scale, nsplit=nsplit,
+                                   partial_ws=ws)
+            proj = self._verify_gemm(attn, layer["wo"], QL)
+            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
+                                           residual=residual,
+                                           eps=cfg.rms_eps)
+            gu = self._verify_gemm(hidden, layer["wgu"], QL)
+            act = ops.swiglu_fused(gu.contiguous())
+            down = self._verify_gemm(act, layer["wdown"], QL)
+            next_norm = w.layers[li + 1]["attn_norm"] \
+                if li + 1 < cfg.num_layers else w.final_norm
+            hidden = ops.fused_add_rmsnorm(down, next_norm,
+                                           residual=residual,
+                                           eps=cfg.rms_eps)
+        logits = getattr(self, "buf_verify_logits", None)
+        if logits is None or logits.shape[1] != QL:
+            logits = self.buf_verify_logits = torch.empty(
+                B, QL, cfg.vocab_size, dtype=torch.bfloat16,
+                device=self.device)
+        logits.view(T, cfg.vocab_size).copy_(
+            self._verify_gemm(hidden, w.lm_head, QL))
+        pred = logits.argmax(dim=-1)  # [B, QL]
+        hits = (drafts == pred[:, :k]).to(torch.int64)
+        n_accepted = hits.cumprod(dim=1).sum(dim=1)  # leading matches
+        self.cache_lens.add_((n_accepted + 1).to(torch.int32)
+                             ).clamp_(max=cfg.max_seq_len)
+        self.buf_tokens.copy_(
+            pred.gather(1, n_accepted.view(B, 1)).view(B))
+        return pred, n_accepted
+
+    def _speculative_loop(self, history: torch.Tensor,
+                          hist_lens: torch.Tensor, start_lens: torch.Tensor,
+                          active: torch.Tensor, max_new_tokens: int,
+                          k: int, ngram: int) -> torch.Tensor:
+        """Draft-and-verify until every active row holds max_new_tokens
+        generated tokens; returns them [B, max_new_tokens].
+
+        history [B, max_seq_len] int64 holds each row's prompt and the
+        tokens generated so far (hist_lens of them, the last one being
+        the pending buf_tokens entry, so cache_lens == hist_lens - 1);
+        start_lens are the prompt lengths.  A row that has its tokens —
+        and every inactive row — is frozen: its cache_lens, buf_tokens
+        and history are put back after each verify pass, so it cannot
+        run past the cache while slower rows catch up.  The one host
+        read per step is the smallest produced count."""
+        B, QL = self.B, k + 1
+        L = history.shape[1]
+        steps = torch.arange(QL, dtype=torch.int64, device=self.device)
+        counters = torch.zeros(2, dtype=torch.int64, device=self.device)
+        big = torch.full((B,), max_new_tokens, dtype=torch.int32,
+                         device=self.device)
+        n_steps = 0
+        produced_min = 1  # the prefill token
+        while produced_min < max_new_tokens:
+            produced = hist_lens - start_lens
+            done = (produced >= max_new_tokens) | ~active
+            drafts = ops.ngram_draft(history, hist_lens, k, n=ngram)
+            lens_before = self.cache_lens.clone()
+            tokens_before = self.buf_tokens.clone()
+            pred, n_accepted = self.verify_step(drafts)
+            self.cache_lens.copy_(
+                torch.where(done, lens_before, self.cache_lens))
+            self.buf_tokens.copy_(
+                torch.where(done, tokens_before, self.buf_tokens))
+            # all QL predictions go to history[b, len..len+QL); only
+            # the first n_accepted + 1 of them become part of it
+            idx = (hist_lens.view(B, 1).long() + steps).clamp_(max=L - 1)
+            vals = torch.where(done.view(B, 1), history.gather(1, idx),
+                               pred)
+            history.scatter_(1, idx, vals)
+            live = ~done
+            hist_lens.add_((live * (n_accepted + 1)).to(torch.int32))
+            counters[0] += live.sum() * k
+            counters[1] += (n_accepted * live).sum()
+            n_steps += 1
+            produced_min = int(torch.where(
+                active, hist_lens - start_lens, big).min())
+        drafted, accepted = counters.tolist()
+        self.spec_stats["steps"] += n_steps
+        self.spec_stats["drafted"] += drafted
+        self.spec_stats["accepted"] += accepted
+        cols = start_lens.view(B, 1).long() + torch.arange(
+            max_new_tokens, dtype=torch.int64, device=self.device)
+        return history.gather(1, cols.clamp_(max=L - 1))
+
+    @torch.no_grad()
+    def generate_speculative(self, tokens: torch.Tensor,
+                             max_new_tokens: int = 32, k: int = 3,
+                             ngram: int = 2) -> torch.Tensor:
+        """Greedy generation, several tokens per pass over the weights:
+        an n-gram lookup in each row's own history drafts k tokens
+        (``ops.ngram_draft``) and ``verify_step`` keeps the prefix that
+        plain greedy decoding would have produced, so the output equals
+        ``generate``'s.  tokens [B, S] -> [B, max_new_tokens].
+        Acceptance counters accumulate in ``spec_stats``."""
+        B, S = tokens.shape
+        assert B == self.B, f"engine built for batch {self.B}, got {B}"
+        self._check_speculative(k)
+        assert S + max_new_tokens + k <= self.cfg.max_seq_len, \
+            "speculative decoding needs room for k drafted tokens: " \
+            f"{S}+{max_new_tokens}+{k} > {self.cfg.max_seq_len}"
+        logits = self.prefill(tokens)
+        self.buf_tokens.copy_(self._select_tokens(logits))
+        history = torch.zeros(B, self.cfg.max_seq_len, dtype=torch.int64,
+                              device=self.device)
+        history[:, :S] = tokens.to(self.device)
+        history[:, S] = self.buf_tokens
+        hist_lens = torch.full((B,), S + 1, dtype=torch.int32,
+                               device=self.device)
+        start_lens = torch.full((B,), S, dtype=torch.int32,
+                                device=self.device)
+        active = torch.ones(B, dtype=torch.bool, device=self.device)
+        return self._speculative_loop(history, hist_lens, start_lens,
+                                      active, max_new_tokens, k, ngram)
+
     def reset(self):
         self.cache_lens.zero_()
 
@@ -832,6 +1039,11 @@ class LlamaServer:
     - ``prefill``: how continuous scheduling prefills an admitted
       group — "exact" (default) one pass per distinct prompt length,
       "packed" one varlen pass over all of them (bf16 KV only)
+    - ``speculative``: k > 0 (at most 7) turns batch scheduling's
+      decode loop into speculative greedy decoding — an n-gram lookup
+      drafts k tokens per step and one verify pass keeps those that
+      greedy decoding would have produced (greedy, bf16 weights and KV,
+      ``scheduling="batch"`` only; default 0 = off)
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -840,7 +1052,8 @@ class LlamaServer:
                  replicas=1, weight_dtype="bf16", kv_dtype="bf16",
                  scheduling="batch", stop_token: int = None,
                  temperature: float = 0.0, top_k: int = 0,
-                 prefill: str = "exact", **class_args):
+                 prefill: str = "exact", speculative: int = 0,
+                 **class_args):
         import queue as queue_mod
         import threading
 
@@ -873,6 +1086,10 @@ class LlamaServer:
         self.stop_token = stop_token  # finish a request at this token
         self.temperature = float(temperature)
         self.top_k = int(top_k)
+        # speculative=k > 0: batch scheduling drafts k tokens per step
+        # by n-gram lookup and verifies them in one pass (greedy, bf16)
+        self.speculative = int(speculative)
+        self._check_speculative_config()
         self.replicas = max(int(replicas), 1)
         self.engines: typing.List[LlamaDecodeEngine] = []
         self.batch_window_ms = batch_window_ms
@@ -886,6 +1103,33 @@ class LlamaServer:
     @property
     def engine(self):
         return self.engines[0] if self.engines else None
+
+    def _check_speculative_config(self):
+        """speculative > 0 only combines with greedy batch scheduling
+        on bf16 weights and a bf16 KV cache; name the conflict."""
+        k = self.speculative
+        if k == 0:
+            return
+        if not 1 <= k <= ops.VERIFY_MAX_QL - 1:
+            raise ValueError(
+                f"speculative={k} is outside [0, {ops.VERIFY_MAX_QL - 1}]")
+        if self.scheduling == "continuous":
+            raise ValueError(
+                f'speculative={k} conflicts with scheduling="continuous" '
+                "(its output ring takes one token per slot per step): "
+                'use scheduling="batch"')
+        if self.temperature != 0.0:
+            raise ValueError(
+                f"speculative={k} conflicts with temperature="
+                f"{self.temperature}: speculative decoding is greedy only")
+        if self.kv_dtype == "fp8":
+            raise ValueError(
+                f'speculative={k} conflicts with kv_dtype="fp8": the '
+                "verify attention kernel reads bf16 caches only")
+        if self.weight_dtype == "fp8w":
+            raise ValueError(
+                f'speculative={k} conflicts with weight_dtype="fp8w": '
+                "the verify pass runs on the bf16 weights")
 
     def post_init(self, mode="sync"):
         stream = getattr(self.context, "stream", None) if self.context \
@@ -918,6 +1162,7 @@ class LlamaServer:
         import threading
 
         cfg = self._build_config()
+        self._check_speculative_config()
         if self.prefill == "packed" and self.kv_dtype == "fp8":
             raise ValueError(
                 'prefill="packed" needs a bf16 KV cache (the packed '
@@ -1345,13 +1590,16 @@ class LlamaServer:
                                   dtype=torch.int64)
             engine.prefill_slots(tokens, torch.tensor(idxs,
                                                       dtype=torch.long))
-        if engine.use_graph and engine._graph is None:
-            engine.capture_graph()
-        generated = [engine.buf_tokens.clone()]
-        for _ in range(max_new - 1):
-            engine.decode_step()
-            generated.append(engine.buf_tokens.clone())
-        out = torch.stack(generated, dim=1)
+        if self.speculative > 0:
+            out = self._speculate_on(engine, prompts, max_new)
+        else:
+            if engine.use_graph and engine._graph is None:
+                engine.capture_graph()
+            generated = [engine.buf_tokens.clone()]
+            for _ in range(max_new - 1):
+                engine.decode_step()
+                generated.append(engine.buf_tokens.clone())
+            out = torch.stack(generated, dim=1)
         rows = out[:n].cpu().tolist()
         if self.stop_token is not None:
             trimmed = []
@@ -1362,8 +1610,43 @@ class LlamaServer:
             return trimmed
         return rows
 
+    def _speculate_on(self, engine: LlamaDecodeEngine, prompts: list,
+                      max_new: int) -> torch.Tensor:
+        """The decode loop of _generate_on in speculative mode: the
+        prompts (already prefilled into rows 0..n-1) seed the draft
+        history, rows beyond them have length 0 and stay frozen."""
+        k = self.speculative
+        n, B = len(prompts), engine.B
+        smax = engine.cfg.max_seq_len
+        longest = max(len(p) for p in prompts)
+        if longest + max_new + k > smax:
+            raise ValueError(
+                f"speculative={k}: a prompt of {longest} tokens plus "
+                f"max_tokens={max_new} plus {k} drafted tokens exceeds "
+                f"max_seq_len {smax}")
+        host = torch.zeros(B, smax, dtype=torch.int64)
+        lens = [len(p) for p in prompts] + [0] * (B - n)
+        for i, prompt in enumerate(prompts):
+            host[i, :len(prompt)] = torch.tensor(prompt, dtype=torch.int64)
+        history = host.to(engine.device)
+        start_lens = torch.tensor(lens, dtype=torch.int32
+                                  ).to(engine.device)
+        active = torch.arange(B, device=engine.device) < n
+        # the prefill token is the first generated one
+        history.scatter_(1, start_lens.view(B, 1).long(),
+                         (engine.buf_tokens * active).view(B, 1))
+        hist_lens = start_lens + active.to(torch.int32)
+        return engine._speculative_loop(history, hist_lens, start_lens,
+                                        active, max_new, k, 2)
+
     def logged_results(self, request, response, op):
         return request.get("inputs"), None
 
     def stats(self):
-        return {}
+        if not self.speculative:
+            return {}
+        totals = {"steps": 0, "drafted": 0, "accepted": 0}
+        for engine in self.engines:
+            for key in totals:
+                totals[key] += engine.spec_stats[key]
+        return {"speculative": totals}

@@ -518,6 +518,139 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor,
     return out
 
 
+# -------------------------------------------------- speculative decoding
+
+VERIFY_MAX_QL = 8       # query rows per sequence in one verify pass
+_VERIFY_WS_ROW = 128 + 4  # f32 per (row, head, split): o[128], m, l, pad
+
+
+def pick_verify_nsplit(B: int, Hkv: int, Smax: int,
+                       target: int = 512) -> int:
+    """Split-S factor for attn_verify.  Measured (scripts/
+    bench_verify.py, B=32, Hkv=8, QL=4): the ~2048 workgroups that suit
+    attn_decode are too many here — a workgroup streams a whole KV head
+    for G x QL columns, two of them fit a CU, and every extra split
+    costs G x QL partial rows of workspace traffic.  Context 1024:
+    ns1 28.8, ns2 28.1, ns4 32.7, ns8 37.4, ns16 50.5 us; context 4096:
+    104.5, 98.6, 101.5, 110.8, 125.2 us.  So aim at ~512 workgroups,
+    capped at 16 and at the 64-key tiles of the cache."""
+    base = max(B * Hkv, 1)
+    n = max(1, target // base)
+    n = 1 << (n.bit_length() - 1)  # round down to a power of two
+    return max(1, min(n, 16, (Smax + 63) // 64))
+
+
+def attn_verify_ws_numel(B: int, QL: int, Hq: int, nsplit: int) -> int:
+    """f32 elements of the split-S workspace ``attn_verify`` needs."""
+    return B * QL * Hq * nsplit * _VERIFY_WS_ROW
+
+
+def attn_verify(q: torch.Tensor, k_cache: torch.Tensor,
+                v_cache: torch.Tensor, base_lens: torch.Tensor,
+                scale: float = None, out: torch.Tensor = None,
+                nsplit: int = None,
+                partial_ws: torch.Tensor = None) -> torch.Tensor:
+    """Speculative-verify GQA attention: a handful of query rows per
+    sequence against a long cached prefix.
+
+    q [B, QL, Hq, D] bf16 (may be a strided view into the fused qkv
+    buffer), caches [B, Hkv, Smax, D] bf16, base_lens [B] int32 = rows
+    cached BEFORE these QL tokens.  Query j of row b sits at position
+    base_lens[b] + j and attends to rows 0..base_lens[b]+j of
+    cache[b, h // G]; the QL new k/v rows must already be in the cache
+    (rope_kv_varlen).  Returns out [B*QL, Hq*D] bf16.
+
+    D = 128, G <= 8, 1 <= QL <= 8, bf16 caches — anything else raises
+    ValueError.  On GPU one workgroup serves a whole KV head (K/V read
+    once for its G q-heads) and the context is split nsplit ways
+    (default: pick_verify_nsplit);
+    pass out/partial_ws (attn_verify_ws_numel) to avoid allocation."""
+    if q.dim() != 4 or k_cache.dim() != 4:
+        raise ValueError("attn_verify: q must be [B, QL, Hq, D] and the "
+                         "caches [B, Hkv, Smax, D]")
+    B, QL, Hq, D = q.shape
+    Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+    if D != 128 or k_cache.shape[3] != D:
+        raise ValueError(f"attn_verify needs head_dim 128, got {D}")
+    if not 1 <= QL <= VERIFY_MAX_QL:
+        raise ValueError(
+            f"attn_verify needs 1 <= QL <= {VERIFY_MAX_QL}, got {QL}")
+    if Hkv < 1 or Hq % Hkv or Hq // Hkv > 8:
+        raise ValueError("attn_verify: q heads per kv head must divide "
+                         f"and be <= 8 (Hq={Hq}, Hkv={Hkv})")
+    if k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16 \
+            or q.dtype != torch.bfloat16:
+        raise ValueError("attn_verify reads bf16 q and bf16 KV caches only")
+    if k_cache.shape[0] != B or base_lens.numel() != B:
+        raise ValueError("attn_verify: q, caches and base_lens must agree "
+                         "on the batch size")
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if out is None:
+        out = torch.empty(B * QL, Hq * D, dtype=q.dtype, device=q.device)
+    if q.is_cuda:
+        ops = _require_hip()
+        if nsplit is None:
+            nsplit = pick_verify_nsplit(B, Hkv, Smax)
+        nsplit = max(int(nsplit), 1)
+        if nsplit > 1 and partial_ws is None:
+            partial_ws = torch.empty(
+                attn_verify_ws_numel(B, QL, Hq, nsplit),
+                dtype=torch.float32, device=q.device)
+        ops.attn_verify(out, q, k_cache, v_cache, base_lens, scale,
+                        partial_ws, nsplit)
+        return out
+    # fp32 reference: the attn_prefill reference with every sequence a
+    # chunk of QL rows on its own cache row
+    cu = torch.arange(B + 1, dtype=torch.int32) * QL
+    slots = torch.arange(B, dtype=torch.int32)
+    return attn_prefill(q.reshape(B * QL, Hq, D), k_cache, v_cache, cu,
+                        slots, base_lens, scale, out=out)
+
+
+def ngram_draft(history: torch.Tensor, hist_lens: torch.Tensor, k: int,
+                n: int = 2, out: torch.Tensor = None) -> torch.Tensor:
+    """Prompt-lookup drafter: propose k tokens per row from the row's
+    own history [B, L] int64 (hist_lens [B] int32 valid tokens each).
+
+    With len = hist_lens[b] clamped to [0, L]: find the LARGEST p with
+    p + n < len and history[b, p:p+n] == history[b, len-n:len]; then
+    drafts[b, j] = history[b, p+n+j] while p+n+j < len.  Every other
+    draft — also when nothing matches or len < n+1 — is the last token
+    history[b, len-1]; len == 0 gives zeros.  Runs on the device
+    without a host round trip; returns drafts [B, k] int64."""
+    if history.dim() != 2 or history.dtype != torch.int64:
+        raise ValueError("ngram_draft: history must be [B, L] int64")
+    k, n = int(k), int(n)
+    if k < 1 or not 1 <= n <= 64:
+        raise ValueError("ngram_draft needs k >= 1 and 1 <= n <= 64")
+    B, L = history.shape
+    if hist_lens.numel() != B:
+        raise ValueError("ngram_draft: one hist_lens entry per row")
+    if out is None:
+        out = torch.empty(B, k, dtype=torch.int64, device=history.device)
+    if history.is_cuda:
+        _require_hip().ngram_draft(out, history, hist_lens, n)
+        return out
+    lens = hist_lens.tolist()
+    for b in range(B):
+        length = max(0, min(int(lens[b]), L))
+        if length == 0:
+            out[b] = 0
+            continue
+        row = history[b, :length].tolist()
+        tail = row[length - n:]
+        match = -1
+        if length >= n + 1:
+            for p in range(length - n - 1, -1, -1):
+                if row[p:p + n] == tail:
+                    match = p
+                    break
+        for j in range(k):
+            src = match + n + j if match >= 0 else length
+            out[b, j] = row[src] if src < length else row[-1]
+    return out
+
+
 def kv_append(k_cache, v_cache, k_new, v_new, positions):
     """Scatter the new token K/V into the cache at positions[b]."""
     if k_cache.is_cuda:

@@ -408,6 +408,87 @@ void attn_prefill(torch::Tensor o, torch::Tensor q, torch::Tensor kc,
                       q_row_stride, (int)max_q_len, stream());
 }
 
+// speculative verify: QL query rows per sequence against the cached
+// prefix; q [B, QL, Hq, D] may be a strided view into the qkv buffer
+void attn_verify(torch::Tensor o, torch::Tensor q, torch::Tensor kc,
+                 torch::Tensor vc, torch::Tensor base_lens, double scale,
+                 c10::optional<torch::Tensor> partial_ws, int64_t nsplit) {
+  CHECK_DEV(o); CHECK_CONTIG(o); CHECK_BF16(o);
+  CHECK_DEV(q); CHECK_BF16(q);
+  CHECK_DEV(kc); CHECK_CONTIG(kc); CHECK_BF16(kc);
+  CHECK_DEV(vc); CHECK_CONTIG(vc); CHECK_BF16(vc);
+  CHECK_DEV(base_lens); CHECK_CONTIG(base_lens); CHECK_I32(base_lens);
+  TORCH_CHECK(q.dim() == 4, "q must be [B, QL, Hq, D]");
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes(),
+              "caches must be [B, Hkv, Smax, D] of equal shape");
+  int64_t B = q.size(0);
+  int QL = q.size(1), Hq = q.size(2), D = q.size(3);
+  int Hkv = kc.size(1), Smax = kc.size(2);
+  TORCH_CHECK(D == 128 && kc.size(3) == D,
+              "attn_verify requires head_dim 128");
+  TORCH_CHECK(QL >= 1 && QL <= 8, "attn_verify needs 1 <= QL <= 8");
+  TORCH_CHECK(Hkv >= 1 && Hq % Hkv == 0 && Hq / Hkv <= 8,
+              "grouped heads per kv head must divide and be <= 8");
+  TORCH_CHECK(kc.size(0) == B && base_lens.numel() == B,
+              "q, caches and base_lens must agree on B");
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(2) == D,
+              "inner dims must be dense (strides (*, *, dim, 1))");
+  // a size-1 dim has no meaningful stride: take the row stride from
+  // the dim that really steps through the rows
+  long long q_row_stride = QL > 1 ? q.stride(1) : q.stride(0);
+  if (B == 1 && QL == 1) q_row_stride = (long long)Hq * D;
+  TORCH_CHECK(QL == 1 || B == 1 || q.stride(0) == QL * q.stride(1),
+              "q rows must be evenly strided over [B, QL]");
+  TORCH_CHECK(q_row_stride >= (long long)Hq * D,
+              "q rows must not overlap");
+  // the kernel reads q and the caches with 16 B vector loads
+  TORCH_CHECK(q_row_stride % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q rows must be 16-byte aligned");
+  TORCH_CHECK(o.numel() == B * QL * Hq * D, "out must be [B*QL, Hq*D]");
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535, "grid too large");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 1024, "bad nsplit");
+  float* ws = nullptr;
+  if (nsplit > 1) {
+    TORCH_CHECK(partial_ws.has_value(), "nsplit>1 needs partial_ws");
+    CHECK_DEV(*partial_ws); CHECK_CONTIG(*partial_ws);
+    CHECK_F32(*partial_ws);
+    TORCH_CHECK(partial_ws->numel() >=
+                B * QL * Hq * nsplit * (int64_t)(D + 4),
+                "partial_ws too small");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(partial_ws->data_ptr()) % 16
+                == 0, "partial_ws must be 16-byte aligned");
+    ws = (float*)partial_ws->data_ptr();
+  }
+  if (B == 0) return;
+  launch_attn_verify(o.data_ptr(), q.data_ptr(), kc.data_ptr(),
+                     vc.data_ptr(), base_lens.data_ptr(), (int)B, QL, Hq,
+                     Hkv, Smax, (float)scale, q_row_stride, ws,
+                     (int)nsplit, stream());
+}
+
+// device-side prompt-lookup drafter
+void ngram_draft(torch::Tensor drafts, torch::Tensor history,
+                 torch::Tensor hist_lens, int64_t n) {
+  CHECK_DEV(drafts); CHECK_CONTIG(drafts);
+  CHECK_DEV(history); CHECK_CONTIG(history);
+  CHECK_DEV(hist_lens); CHECK_CONTIG(hist_lens); CHECK_I32(hist_lens);
+  TORCH_CHECK(drafts.scalar_type() == torch::kInt64 &&
+              history.scalar_type() == torch::kInt64,
+              "drafts and history must be int64");
+  TORCH_CHECK(history.dim() == 2 && drafts.dim() == 2,
+              "history [B, L], drafts [B, k]");
+  int64_t B = history.size(0), L = history.size(1), k = drafts.size(1);
+  TORCH_CHECK(drafts.size(0) == B && hist_lens.numel() == B,
+              "drafts, history and hist_lens must agree on B");
+  TORCH_CHECK(n >= 1 && n <= 64, "ngram_draft needs 1 <= n <= 64");
+  TORCH_CHECK(L < (1LL << 30) && k < (1LL << 20), "shape too large");
+  if (B == 0 || k == 0) return;
+  launch_ngram_draft(drafts.data_ptr(), history.data_ptr(),
+                     hist_lens.data_ptr(), (int)B, (int)L, (int)k, (int)n,
+                     stream());
+}
+
 void softmax(torch::Tensor out, torch::Tensor in) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(in); CHECK_CONTIG(in); CHECK_BF16(in);
@@ -559,6 +640,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("slots"), py::arg("kv_start"), py::arg("scale"),
         py::arg("max_q_len"),
         "packed causal GQA flash-attention prefill over the KV cache");
+  m.def("attn_verify", &attn_verify, py::arg("o"), py::arg("q"),
+        py::arg("kc"), py::arg("vc"), py::arg("base_lens"),
+        py::arg("scale"), py::arg("partial_ws") = py::none(),
+        py::arg("nsplit") = 1,
+        "speculative verify attention (QL query rows per sequence)");
+  m.def("ngram_draft", &ngram_draft, py::arg("drafts"), py::arg("history"),
+        py::arg("hist_lens"), py::arg("n"),
+        "device-side prompt-lookup (n-gram) drafter");
   m.def("softmax", &softmax, "row softmax (bf16)");
   m.def("tree_ensemble", &tree_ensemble, "GBDT ensemble inference (f32)");
   m.def("window_ingest", &window_ingest,

@@ -92,6 +92,16 @@ void launch_attn_prefill(void* O, const void* Q, const void* Kc,
                          float scale, long long q_row_stride,
                          int max_q_len, void* stream);
 
+void launch_attn_verify(void* O, const void* Q, const void* Kc,
+                        const void* Vc, const void* base_lens, int B,
+                        int QL, int Hq, int Hkv, int Smax, float scale,
+                        long long q_row_stride, float* partial_ws,
+                        int nsplit, void* stream);
+
+void launch_ngram_draft(void* drafts, const void* history,
+                        const void* hist_lens, int B, int L, int k, int n,
+                        void* stream);
+
 void launch_softmax(void* out, const void* in, int rows, int cols,
                     void* stream);
 

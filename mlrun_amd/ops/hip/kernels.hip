@@ -2134,6 +2134,353 @@ void launch_attn_prefill(void* O, const void* Q, const void* Kc,
 }
 
 // ---------------------------------------------------------------------
+// Speculative verify attention: QL (1..8) query rows per sequence
+// against a long cached prefix.
+//
+//   query j of batch row b sits at position base_lens[b] + j and
+//   attends to rows 0..base_lens[b]+j of cache[b, h / G]; the QL new
+//   K/V rows are already in the cache (rope_kv_varlen).
+//
+// grid (nsplit, Hkv, B); block 256 = 4 waves.  A workgroup owns ONE
+// (batch row, KV head): the G x QL (q-head, query) pairs that share this
+// KV head are the columns of attn_prefill's transposed tiles
+// (column c = g * QL + j, <= 64 of them, 16 per wave), so K/V are read
+// from HBM once per KV head instead of once per q-head, and a column
+// tile is as full as G x QL allows (G=4, QL=4: exactly 16).  The two
+// products, the register-resident P, the transposed V read and the
+// staging (zeros at and past base + QL) are attn_prefill's.  Waves
+// whose column tile is empty only help with staging: the kernel is
+// bound by the K/V stream, not by the MFMAs of its one or two busy
+// waves (32 MFMAs per 32 KB tile).
+//
+// The causal mask is per column (key > base + j) and is applied only
+// on tiles that reach past `base`.  A column that sees no key in a
+// tile keeps m = -1e30, l = 0, o = 0 (finite, zero weight).
+//
+// Split-S: the row's 64-key tiles are dealt to ns = min(nsplit, tiles)
+// splits in contiguous ranges (never an empty range); blocks of the
+// remaining splits exit at once, and the combine kernel derives the
+// same ns from base_lens.  A split writes unnormalised f32 partials
+// (o[128], m, l; m in the log2 domain) per column with plain stores;
+// attn_verify_combine_kernel folds them with exp2.  nsplit == 1 writes
+// bf16 directly.  A row with base < 0 or base + QL > Smax is skipped in
+// both kernels (block-uniform, before any barrier).
+// ---------------------------------------------------------------------
+#define VF_WS_ROW (128 + 4)  // o[128], m, l, pad: rows stay 16 B aligned
+
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void attn_verify_kernel(
+    unsigned short* __restrict__ O, float* __restrict__ ws,
+    const unsigned short* __restrict__ Q,
+    const unsigned short* __restrict__ Kc,
+    const unsigned short* __restrict__ Vc,
+    const int* __restrict__ base_lens, int QL, int Hq, int Hkv, int Smax,
+    float scale_log2e, long long q_row_stride, int nsplit) {
+  constexpr int D = 128;
+  __shared__ __attribute__((aligned(16)))
+      unsigned short lds[2 * PF_BN * PF_ROW];
+  unsigned short* kbuf = lds;
+  unsigned short* vbuf = lds + PF_BN * PF_ROW;
+
+  const int split = blockIdx.x;
+  const int kvh = blockIdx.y;
+  const int b = blockIdx.z;
+  // --- block-uniform setup and early exits (before any barrier)
+  const int base = base_lens[b];
+  if (base < 0 || base + QL > Smax) return;
+  const int kv_end = base + QL;  // keys this row sees, <= Smax
+  const int ntiles = (kv_end + PF_BN - 1) / PF_BN;
+  const int ns = min(nsplit, ntiles);
+  if (split >= ns) return;
+  const int t_begin = (split * ntiles) / ns;
+  const int t_end = ((split + 1) * ntiles) / ns;
+
+  const int G = Hq / Hkv;
+  const int ncols = G * QL;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int lq = lane & 15;  // column of the transposed tiles
+  const int lh = lane >> 4;
+  const bool wave_active = wave * 16 < ncols;
+  const int col = wave * 16 + lq;
+  const bool col_valid = col < ncols;
+  const int cc = min(col, ncols - 1);
+  const int g = cc / QL;
+  const int j = cc - g * QL;
+  const int h = kvh * G + g;
+  const int pos = base + j;  // this lane's query position
+  const size_t qrow = (size_t)b * QL + j;
+
+  // --- Q fragments: loaded once, live across the whole tile loop
+  short8v qf[4];
+  {
+    const unsigned short* qp =
+        Q + qrow * q_row_stride + (size_t)h * D + lh * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      qf[ks] = *reinterpret_cast<const short8v*>(qp + ks * 32);
+  }
+
+  const size_t cbase = ((size_t)b * Hkv + kvh) * Smax * D;
+  const unsigned short* kbase = Kc + cbase;
+  const unsigned short* vbase = Vc + cbase;
+
+  // staging: 64 rows x 16 chunks of 16 B = 4 chunks per thread
+  short8v kreg[4], vreg[4];
+  auto issue = [&](int tile0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      const int key = tile0 + (c >> 4);
+      const short8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
+      kreg[i] = zero;
+      vreg[i] = zero;
+      if (key < kv_end) {
+        const size_t off = (size_t)key * D + (c & 15) * 8;
+        kreg[i] = *reinterpret_cast<const short8v*>(kbase + off);
+        vreg[i] = *reinterpret_cast<const short8v*>(vbase + off);
+      }
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      const int off = (c >> 4) * PF_ROW + (c & 15) * 8;
+      *reinterpret_cast<short8v*>(kbuf + off) = kreg[i];
+      *reinterpret_cast<short8v*>(vbuf + off) = vreg[i];
+    }
+  };
+
+  f32x4v o[8];
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) o[dt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  float m = -1e30f;  // running column max (log2 domain), finite on purpose
+  float l = 0.f;     // this lane's share of the column sum
+
+  issue(t_begin * PF_BN);
+  for (int t = t_begin; t < t_end; ++t) {
+    const int tile0 = t * PF_BN;
+    __syncthreads();  // everyone is done reading the previous tile
+    commit();
+    __syncthreads();
+    if (t + 1 < t_end) issue(tile0 + PF_BN);  // flies under the MFMAs
+    if (!wave_active) continue;
+
+    // --- S^T = K . Q^T : 4 key tiles x 4 k-steps
+    f32x4v s[4];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      s[kt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      const unsigned short* kp = kbuf + (kt * 16 + lq) * PF_ROW + lh * 8;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const short8v kf = *reinterpret_cast<const short8v*>(kp + ks * 32);
+        s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[kt],
+                                                        0, 0, 0);
+      }
+    }
+    // --- scale, per-column causal mask on the tiles past `base`, max
+    const bool need_mask = tile0 + PF_BN - 1 > base;
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = s[kt][r] * scale_log2e;
+        if (need_mask && tile0 + kt * 16 + lh * 4 + r > pos)
+          x = -__builtin_inff();
+        s[kt][r] = x;
+        mx = fmaxf(mx, x);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    // --- online softmax; a column with no visible key in this tile has
+    // mx = -inf: m stays put, alpha = 1 and every p = exp2(-inf) = 0
+    const float m_new = fmaxf(m, mx);
+    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+    m = m_new;
+    float psum = 0.f;
+    short8v pb[2];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_new);
+        psum += p;
+        pb[kt >> 1][(kt & 1) * 4 + r] = pf_f2bf(p);
+      }
+    }
+    l = l * alpha + psum;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
+    // --- O^T += V^T . P^T : 8 dim tiles x 2 k-steps of 32 keys
+    const unsigned short* vp =
+        vbuf + (lh * 4 + (lq >> 2)) * PF_ROW + (lq & 3) * 4;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const short4v lo = pf_read_tr16(vp + (ks * 32) * PF_ROW + dt * 16);
+        const short4v hi =
+            pf_read_tr16(vp + (ks * 32 + 16) * PF_ROW + dt * 16);
+        const short8v vf =
+            __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks], o[dt],
+                                                        0, 0, 0);
+      }
+    }
+  }
+
+  // --- epilogue: finish the column sum across its 4 lanes
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (!col_valid) return;
+  const size_t orow = qrow * Hq + h;
+  if (!SPLIT) {
+    const float inv = (l > 0.f) ? 1.f / l : 0.f;
+    unsigned short* op = O + orow * D + lh * 4;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+      ushort4 w;
+      w.x = f2bf(o[dt][0] * inv);
+      w.y = f2bf(o[dt][1] * inv);
+      w.z = f2bf(o[dt][2] * inv);
+      w.w = f2bf(o[dt][3] * inv);
+      *reinterpret_cast<ushort4*>(op + dt * 16) = w;
+    }
+  } else {
+    float* prow = ws + (orow * nsplit + split) * VF_WS_ROW;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt)
+      *reinterpret_cast<f32x4v*>(prow + dt * 16 + lh * 4) = o[dt];
+    if (lh == 0) {
+      prow[D] = m;
+      prow[D + 1] = l;
+    }
+  }
+}
+
+// fold the split partials: one wave per output row (b, j, h); the same
+// guard and the same split count as attn_verify_kernel
+__global__ void attn_verify_combine_kernel(
+    unsigned short* __restrict__ O, const float* __restrict__ ws,
+    const int* __restrict__ base_lens, int QL, int Hq, int Smax,
+    int nsplit) {
+  constexpr int D = 128;
+  const int row = blockIdx.x;  // (b * QL + j) * Hq + h
+  const int lane = threadIdx.x;
+  const int base = base_lens[row / (QL * Hq)];
+  if (base < 0 || base + QL > Smax) return;
+  const int ntiles = (base + QL + PF_BN - 1) / PF_BN;
+  const int ns = min(nsplit, ntiles);
+  const float* part = ws + (size_t)row * nsplit * VF_WS_ROW;
+  float m_star = -1e30f;
+  for (int s = 0; s < ns; ++s)
+    m_star = fmaxf(m_star, part[s * VF_WS_ROW + D]);
+  float l_total = 0.f, a0 = 0.f, a1 = 0.f;
+  for (int s = 0; s < ns; ++s) {
+    const float* prow = part + s * VF_WS_ROW;
+    // log2 domain, like the partials; an empty column (m = -1e30)
+    // weighs exp2(-huge) = 0 against any real max
+    const float wgt = __builtin_amdgcn_exp2f(prow[D] - m_star);
+    l_total += wgt * prow[D + 1];
+    a0 += wgt * prow[lane * 2];
+    a1 += wgt * prow[lane * 2 + 1];
+  }
+  const float inv = (l_total > 0.f) ? 1.f / l_total : 0.f;
+  unsigned short* op = O + (size_t)row * D + lane * 2;
+  op[0] = f2bf(a0 * inv);
+  op[1] = f2bf(a1 * inv);
+}
+
+void launch_attn_verify(void* O, const void* Q, const void* Kc,
+                        const void* Vc, const void* base_lens, int B,
+                        int QL, int Hq, int Hkv, int Smax, float scale,
+                        long long q_row_stride, float* partial_ws,
+                        int nsplit, void* stream) {
+  if (B <= 0) return;
+  const float sl2 = scale * 1.4426950408889634f;
+  if (nsplit <= 1 || partial_ws == nullptr) {
+    hipLaunchKernelGGL(attn_verify_kernel<false>, dim3(1, Hkv, B),
+                       dim3(256), 0, (hipStream_t)stream,
+                       (unsigned short*)O, (float*)nullptr,
+                       (const unsigned short*)Q, (const unsigned short*)Kc,
+                       (const unsigned short*)Vc, (const int*)base_lens, QL,
+                       Hq, Hkv, Smax, sl2, q_row_stride, 1);
+    return;
+  }
+  hipLaunchKernelGGL(attn_verify_kernel<true>, dim3(nsplit, Hkv, B),
+                     dim3(256), 0, (hipStream_t)stream, (unsigned short*)O,
+                     partial_ws, (const unsigned short*)Q,
+                     (const unsigned short*)Kc, (const unsigned short*)Vc,
+                     (const int*)base_lens, QL, Hq, Hkv, Smax, sl2,
+                     q_row_stride, nsplit);
+  hipLaunchKernelGGL(attn_verify_combine_kernel, dim3(B * QL * Hq),
+                     dim3(64), 0, (hipStream_t)stream, (unsigned short*)O,
+                     (const float*)partial_ws, (const int*)base_lens, QL,
+                     Hq, Smax, nsplit);
+}
+
+// ---------------------------------------------------------------------
+// Prompt-lookup (n-gram) drafter, device side: for each row find the
+// LATEST earlier occurrence of the row's last n tokens and propose the
+// k tokens that followed it.
+//   len = clamp(hist_lens[b], 0, L)
+//   p*  = max p with p + n < len and hist[p..p+n) == hist[len-n..len)
+//   drafts[b, j] = hist[p* + n + j] while p* + n + j < len,
+//                  else hist[len - 1]   (also when there is no match)
+//   len == 0 -> zeros
+// One workgroup (256 threads) per row: lanes scan the candidate
+// positions, a max-reduction picks the latest match.
+// ---------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ngram_draft_kernel(
+    long long* __restrict__ drafts, const long long* __restrict__ history,
+    const int* __restrict__ hist_lens, int L, int k, int n) {
+  __shared__ int wave_best[4];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const long long* hist = history + (size_t)b * L;
+  const int len = max(0, min(hist_lens[b], L));
+  int best = -1;
+  if (len >= n + 1) {
+    const long long* tail = hist + (len - n);
+    for (int p = tid; p + n < len; p += 256) {
+      bool eq = true;
+      for (int i = 0; i < n; ++i) eq = eq && (hist[p + i] == tail[i]);
+      if (eq) best = p;  // p grows: the last hit is this lane's latest
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+    best = max(best, __shfl_xor(best, off, 64));
+  if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+  __syncthreads();
+  best = max(max(wave_best[0], wave_best[1]),
+             max(wave_best[2], wave_best[3]));
+  for (int j = tid; j < k; j += 256) {
+    long long tok = 0;
+    if (len > 0) {
+      const int src = (best >= 0) ? best + n + j : len;
+      tok = hist[src < len ? src : len - 1];
+    }
+    drafts[(size_t)b * k + j] = tok;
+  }
+}
+
+void launch_ngram_draft(void* drafts, const void* history,
+                        const void* hist_lens, int B, int L, int k, int n,
+                        void* stream) {
+  if (B <= 0 || k <= 0) return;
+  hipLaunchKernelGGL(ngram_draft_kernel, dim3(B), dim3(256), 0,
+                     (hipStream_t)stream, (long long*)drafts,
+                     (const long long*)history, (const int*)hist_lens, L, k,
+                     n);
+}
+
+// ---------------------------------------------------------------------
 // Row softmax (bf16 in/out, online single pass over LDS-staged row,
 // used by classic-model servers & tests)
 // ---------------------------------------------------------------------
