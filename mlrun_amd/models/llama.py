@@ -150,15 +150,129 @@ def _training_state_to_decode(state: dict) -> dict:
     return {k: v.to(torch.bfloat16) for k, v in out.items()}
 
 
+LORA_PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
+
+
+class LoraTables:
+    """Adapter tables of a multi-LoRA engine: per layer and projection
+    ``A [NA, R, K]`` and ``Bm [NA, N, R]`` bf16, zero-initialised and
+    allocated once (a captured decode graph keeps their pointers).
+    A slot holds one adapter; adapters of a smaller rank are zero-padded
+    to R and ``alpha / r`` is folded into Bm.  Replica engines share one
+    instance, like they share the weights."""
+
+    def __init__(self, weights: LlamaWeights, max_adapters: int,
+                 rank: int = 16):
+        if rank not in ops.LORA_RANKS:
+            raise ValueError(f"lora_rank must be one of {ops.LORA_RANKS}, "
+                             f"got {rank}")
+        if max_adapters < 1:
+            raise ValueError("LoraTables needs max_adapters >= 1")
+        self.max_adapters = int(max_adapters)
+        self.rank = int(rank)
+        self.weights = weights
+        self.loaded = set()  # slots holding an adapter
+        bf16 = dict(dtype=torch.bfloat16, device=weights.device)
+        self.layers = []
+        for layer in weights.layers:
+            tables = {}
+            for proj in LORA_PROJECTIONS:
+                n, k = layer[proj].shape
+                tables[proj] = (
+                    torch.zeros(self.max_adapters, self.rank, k, **bf16),
+                    torch.zeros(self.max_adapters, n, self.rank, **bf16))
+            self.layers.append(tables)
+
+    def _check_slot(self, slot):
+        if not 0 <= int(slot) < self.max_adapters:
+            raise ValueError(f"adapter slot {slot} outside "
+                             f"[0, {self.max_adapters})")
+        return int(slot)
+
+    def unload(self, slot: int):
+        slot = self._check_slot(slot)
+        for tables in self.layers:
+            for a_tab, b_tab in tables.values():
+                a_tab[slot].zero_()
+                b_tab[slot].zero_()
+        self.loaded.discard(slot)
+
+    @torch.no_grad()
+    def load(self, slot: int, state: dict):
+        """Validate the whole state first, then overwrite the slot."""
+        slot = self._check_slot(slot)
+        if "alpha" not in state:
+            raise ValueError("adapter state has no 'alpha'")
+        alpha = float(state["alpha"])
+        pending = []
+        seen = set()
+        for key in state:
+            if not key.startswith("layers."):
+                continue
+            parts = key.split(".")
+            if len(parts) != 4 or not parts[1].isdigit() or \
+                    parts[2] not in LORA_PROJECTIONS or \
+                    parts[3] not in ("lora_A", "lora_B") or \
+                    int(parts[1]) >= len(self.layers):
+                raise ValueError(f"unexpected adapter key {key!r}")
+            seen.add((int(parts[1]), parts[2]))
+        for li, proj in sorted(seen):
+            key_a = f"layers.{li}.{proj}.lora_A"
+            key_b = f"layers.{li}.{proj}.lora_B"
+            for key in (key_a, key_b):
+                if key not in state:
+                    raise ValueError(f"adapter state lacks {key!r}")
+            mat_a, mat_b = state[key_a], state[key_b]
+            n, k = self.weights.layers[li][proj].shape
+            if mat_a.dim() != 2 or mat_a.shape[1] != k:
+                raise ValueError(f"{key_a}: expected [r, {k}], got "
+                                 f"{tuple(mat_a.shape)}")
+            r = mat_a.shape[0]
+            if not 1 <= r <= self.rank:
+                raise ValueError(f"{key_a}: rank {r} outside "
+                                 f"[1, lora_rank={self.rank}]")
+            if tuple(mat_b.shape) != (n, r):
+                raise ValueError(f"{key_b}: expected [{n}, {r}], got "
+                                 f"{tuple(mat_b.shape)}")
+            pending.append((li, proj, r, mat_a, mat_b))
+        self.unload(slot)
+        for li, proj, r, mat_a, mat_b in pending:
+            a_tab, b_tab = self.layers[li][proj]
+            a_tab[slot, :r].copy_(mat_a)
+            # B * alpha / r in f32, ONE rounding to bf16
+            scaled = mat_b.to(device=b_tab.device, dtype=torch.float32) \
+                * (alpha / r)
+            b_tab[slot, :, :r].copy_(scaled)
+        self.loaded.add(slot)
+
+
 class LlamaDecodeEngine:
     """Batched generation engine: prefill (hipBLASLt+SDPA) + hipGraph-
-    captured decode step on the custom kernel chain."""
+    captured decode step on the custom kernel chain.
+
+    Multi-LoRA (``max_adapters > 0``): every cache slot carries an
+    adapter id in ``buf_adapter`` (-1 = base model); the decode step adds
+    each row's low-rank delta after the four projection GEMMs with the
+    batched ``ops.lora_shrink`` / ``ops.lora_expand`` pair, so ONE
+    captured graph serves rows of different adapters.  Single GPU, no
+    speculative decoding."""
 
     def __init__(self, cfg: LlamaConfig, batch_size: int, device=None,
                  tp_group=None, tp_rank=0, tp_size=1, use_graph=True,
                  seed=1234, weights: "LlamaWeights" = None,
                  weight_dtype: str = "bf16", kv_dtype: str = "bf16",
-                 temperature: float = 0.0, top_k: int = 0):
+                 temperature: float = 0.0, top_k: int = 0,
+                 max_adapters: int = 0, lora_rank: int = 16,
+                 lora: "LoraTables" = None):
+        if (max_adapters > 0 or lora is not None) and tp_size > 1:
+            raise ValueError(
+                f"max_adapters={max_adapters} conflicts with tp_size="
+                f"{tp_size}: LoRA adapters are not sharded")
+        if (max_adapters > 0 or lora is not None) and \
+                batch_size > ops.LORA_MAX_ROWS:
+            raise ValueError(
+                f"max_adapters > 0 needs batch_size <= "
+                f"{ops.LORA_MAX_ROWS}, got {batch_size}")
         self.cfg = cfg
         self.B = batch_size
         self.device = torch.device(
@@ -276,6 +390,19 @@ class LlamaDecodeEngine:
             device=self.device) if self.on_gpu else None
         self._graph = None
         self._ksplits = {}
+        # multi-LoRA (opt-in): shared adapter tables + per-slot ids.
+        # With max_adapters == 0 nothing is allocated and the decode
+        # step takes exactly the path it takes without this feature.
+        if lora is None and max_adapters > 0:
+            lora = LoraTables(w, max_adapters, lora_rank)
+        self.lora = lora
+        self.max_adapters = lora.max_adapters if lora is not None else 0
+        if lora is not None:
+            self.buf_adapter = torch.full((B,), -1, dtype=torch.int32,
+                                          device=self.device)
+            self.buf_lora_t = torch.zeros(B, lora.rank,
+                                          dtype=torch.float32,
+                                          device=self.device)
         # speculative decoding (opt-in): running acceptance counters
         self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
 
@@ -323,6 +450,89 @@ class LlamaDecodeEngine:
             all_reduce_tensor(t, group=self.tp_group)
         return t
 
+    # ------------------------------------------------------------ lora
+    def load_adapter(self, slot: int, state: dict):
+        """Load a LoRA adapter into table slot ``slot`` (shared by every
+        replica built with ``lora=``).  ``state`` maps
+        ``layers.{i}.{proj}.lora_A`` -> [r, K] and ``.lora_B`` -> [N, r]
+        for any subset of layers and of the projections wqkv / wo / wgu /
+        wdown, plus ``alpha``; r <= lora_rank, missing entries stay zero.
+        A shape that does not fit the weights is a ValueError naming the
+        key.  For an IDLE engine only: the tables are written in place
+        under the captured graph, so no request may be decoding."""
+        if self.lora is None:
+            raise ValueError("engine built with max_adapters=0 holds no "
+                             "adapter tables")
+        self.lora.load(slot, state)
+
+    def unload_adapter(self, slot: int):
+        """Zero table slot ``slot`` (idle engine only, like
+        load_adapter): rows that still name it then get a zero delta."""
+        if self.lora is None:
+            raise ValueError("engine built with max_adapters=0 holds no "
+                             "adapter tables")
+        self.lora.unload(slot)
+
+    def _lora_decode(self, li, proj, x, y):
+        """y[b] += Bm[id_b] (A[id_b] x[b]) for the decode rows, by
+        buf_adapter: two launches, rows with id -1 exit at once."""
+        a_tab, b_tab = self.lora.layers[li][proj]
+        ops.lora_shrink(x, a_tab, self.buf_adapter, out=self.buf_lora_t)
+        ops.lora_expand(y, self.buf_lora_t, b_tab, self.buf_adapter)
+
+    def _adapter_plan(self, adapters, slots, counts):
+        """Prefill side of ``adapters=``: validate one id per prompt
+        (-1 = base), record them in buf_adapter for ``slots`` and return
+        the plan _lora_prefill consumes — a list of (id, row mask or
+        None), one entry per DISTINCT adapter id of the call, with
+        counts[i] token rows for prompt i.  None when no row is adapted.
+        The host knows the ids, so nothing here syncs."""
+        if adapters is None:
+            if self.lora is not None:
+                self.buf_adapter[slots] = -1
+            return None
+        ids = [int(a) for a in adapters]
+        if self.lora is None:
+            if any(a >= 0 for a in ids):
+                raise ValueError("adapters= needs an engine built with "
+                                 "max_adapters > 0")
+            return None
+        if len(ids) != len(counts):
+            raise ValueError(f"adapters has {len(ids)} ids for "
+                             f"{len(counts)} prompts")
+        for a in ids:
+            if not -1 <= a < self.max_adapters:
+                raise ValueError(f"adapter id {a} outside "
+                                 f"[-1, {self.max_adapters})")
+        self.buf_adapter[slots] = torch.tensor(
+            ids, dtype=torch.int32).to(self.device)
+        distinct = sorted({a for a in ids if a >= 0})
+        if not distinct:
+            return None
+        if len(set(ids)) == 1:
+            return [(distinct[0], None)]  # every row, no mask needed
+        row_ids = torch.tensor(
+            [a for a, count in zip(ids, counts) for _ in range(count)],
+            dtype=torch.int32).to(self.device)
+        return [(a, (row_ids == a).unsqueeze(1)) for a in distinct]
+
+    def _lora_prefill(self, plan, li, proj, x, y):
+        """Add the adapters' deltas to a prefill projection output
+        y = x @ W^T ([T, N] bf16): f32 math, one rounding, one pass per
+        distinct id.  Each pass runs over ALL T rows and is masked to
+        its own rows, so a row's result cannot depend on which other
+        adapters share the call (a library GEMM may round a row
+        differently when its row count changes)."""
+        if plan is None:
+            return y
+        a_tab, b_tab = self.lora.layers[li][proj]
+        xf = x.float()
+        for a, mask in plan:
+            delta = (xf @ a_tab[a].float().t()) @ b_tab[a].float().t()
+            new = (y.float() + delta).to(y.dtype)
+            y = new if mask is None else torch.where(mask, new, y)
+        return y
+
     # ---------------------------------------------------------- decode
     def _decode_step_body(self):
         """One token step for all B sequences.  Reads buf_tokens,
@@ -362,6 +572,11 @@ class LlamaDecodeEngine:
         use_slabs = on and self.weight_dtype == "bf16" and \
             self.kv_dtype == "bf16"  # qkv slab (bf16 caches only)
         use_norm_slabs = on and mode == "all" 
+        lora = self.lora is not None
+        if lora:
+            # the adapter delta has to land on the bf16 GEMM output
+            # before rope / norm: the slab-fused consumers are bypassed
+            use_slabs = use_norm_slabs = False
         for li, layer in enumerate(w.layers):
             # qkv projection -> rope -> caches
             done = 0
@@ -376,6 +591,9 @@ class LlamaDecodeEngine:
             if not done:
                 self._gemm(self.buf_hidden, layer["wqkv"], self.buf_qkv,
                            a8=h8, a_scale=h8s)
+                if lora:
+                    self._lora_decode(li, "wqkv", self.buf_hidden,
+                                      self.buf_qkv)
                 ops.rope_kv_fused(self.buf_qkv, self.k_cache[li],
                                   self.v_cache[li], positions,
                                   self.cos_sin, w.hq,
@@ -401,6 +619,9 @@ class LlamaDecodeEngine:
                         layer["ffn_norm"], done, cfg.rms_eps)
             if not done:
                 self._gemm(self.buf_attn_out, layer["wo"], self.buf_proj)
+                if lora:
+                    self._lora_decode(li, "wo", self.buf_attn_out,
+                                      self.buf_proj)
                 self._maybe_allreduce(self.buf_proj)
                 ops.fused_add_rmsnorm(self.buf_proj, layer["ffn_norm"],
                                       residual=self.buf_residual,
@@ -417,6 +638,9 @@ class LlamaDecodeEngine:
             if not done:
                 self._gemm(self.buf_hidden, layer["wgu"], self.buf_gu,
                            a8=h8, a_scale=h8s)
+                if lora:
+                    self._lora_decode(li, "wgu", self.buf_hidden,
+                                      self.buf_gu)
                 ops.swiglu_fused(self.buf_gu, out=self.buf_act)
             next_norm = w.layers[li + 1]["attn_norm"] \
                 if li + 1 < cfg.num_layers else w.final_norm
@@ -431,6 +655,9 @@ class LlamaDecodeEngine:
                         next_norm, done, cfg.rms_eps)
             if not done:
                 self._gemm(self.buf_act, layer["wdown"], self.buf_down)
+                if lora:
+                    self._lora_decode(li, "wdown", self.buf_act,
+                                      self.buf_down)
                 self._maybe_allreduce(self.buf_down)
                 ops.fused_add_rmsnorm(self.buf_down, next_norm,
                                       residual=self.buf_residual,
@@ -559,12 +786,16 @@ class LlamaDecodeEngine:
         return None if self.v_scale is None else self.v_scale[li]
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor) -> torch.Tensor:
+    def prefill(self, tokens: torch.Tensor, adapters=None
+                ) -> torch.Tensor:
         """Process prompts [B, S]; fill KV caches; return last-token
-        logits [B, vocab].  hipBLASLt GEMMs + SDPA."""
+        logits [B, vocab].  hipBLASLt GEMMs + SDPA.  ``adapters``: one
+        LoRA table slot per prompt (-1 = base model, the default); the
+        ids stay in buf_adapter for the decode steps that follow."""
         cfg, w = self.cfg, self.weights
         B, S = tokens.shape
         d = cfg.head_dim
+        plan = self._adapter_plan(adapters, slice(0, B), [S] * B)
         tokens = tokens.to(self.device)
         x = w.embed[tokens.reshape(-1)]  # [B*S, H]
         residual = x.contiguous()
@@ -573,7 +804,8 @@ class LlamaDecodeEngine:
         hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
                              eps=cfg.rms_eps)
         for li, layer in enumerate(w.layers):
-            qkv = hidden @ layer["wqkv"].t()
+            qkv = self._lora_prefill(plan, li, "wqkv", hidden,
+                                     hidden @ layer["wqkv"].t())
             q = qkv[:, :w.hq * d].reshape(B * S, w.hq, d).contiguous()
             k = qkv[:, w.hq * d:(w.hq + w.hkv) * d].reshape(
                 B * S, w.hkv, d).contiguous()
@@ -596,14 +828,17 @@ class LlamaDecodeEngine:
             attn = torch.nn.functional.scaled_dot_product_attention(
                 qh, kc, vc, is_causal=True, enable_gqa=True)
             attn = attn.transpose(1, 2).reshape(B * S, w.hq * d)
-            proj = attn @ layer["wo"].t()
+            proj = self._lora_prefill(plan, li, "wo", attn,
+                                      attn @ layer["wo"].t())
             self._maybe_allreduce(proj)
             hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
                                            residual=residual,
                                            eps=cfg.rms_eps)
-            gu = hidden @ layer["wgu"].t()
+            gu = self._lora_prefill(plan, li, "wgu", hidden,
+                                    hidden @ layer["wgu"].t())
             act = ops.swiglu_fused(gu.contiguous())
-            down = act @ layer["wdown"].t()
+            down = self._lora_prefill(plan, li, "wdown", act,
+                                      act @ layer["wdown"].t())
             self._maybe_allreduce(down)
             next_norm = w.layers[li + 1]["attn_norm"] \
                 if li + 1 < cfg.num_layers else w.final_norm
@@ -617,18 +852,20 @@ class LlamaDecodeEngine:
 
     @torch.no_grad()
     def prefill_slots(self, tokens: torch.Tensor,
-                      slots: torch.Tensor) -> torch.Tensor:
+                      slots: torch.Tensor, adapters=None) -> torch.Tensor:
         """Continuous-batching admission: prefill B' <= B prompts and
         scatter their KV/state into cache rows ``slots``, leaving the
         other slots' caches and lengths untouched.  Returns last-token
         logits [B'].  (Runs the same prefill math on a temporary
-        B'-sized view; decode then advances ALL slots each step.)"""
+        B'-sized view; decode then advances ALL slots each step.)
+        ``adapters``: one LoRA table slot per prompt (-1 = base)."""
         cfg, w = self.cfg, self.weights
         Bp, S = tokens.shape
         slots = torch.as_tensor(slots, dtype=torch.long,
                                 device=self.device)
         assert Bp == slots.numel() and Bp <= self.B
         assert S < cfg.max_seq_len
+        plan = self._adapter_plan(adapters, slots, [S] * Bp)
         d = cfg.head_dim
         tokens = tokens.to(self.device)
         x = w.embed[tokens.reshape(-1)]
@@ -638,7 +875,8 @@ class LlamaDecodeEngine:
         hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
                              eps=cfg.rms_eps)
         for li, layer in enumerate(w.layers):
-            qkv = hidden @ layer["wqkv"].t()
+            qkv = self._lora_prefill(plan, li, "wqkv", hidden,
+                                     hidden @ layer["wqkv"].t())
             q = qkv[:, :w.hq * d].reshape(Bp * S, w.hq, d).contiguous()
             k = qkv[:, w.hq * d:(w.hq + w.hkv) * d].reshape(
                 Bp * S, w.hkv, d).contiguous()
@@ -661,14 +899,17 @@ class LlamaDecodeEngine:
             attn = torch.nn.functional.scaled_dot_product_attention(
                 qh, kc, vc, is_causal=True, enable_gqa=True)
             attn = attn.transpose(1, 2).reshape(Bp * S, w.hq * d)
-            proj = attn @ layer["wo"].t()
+            proj = self._lora_prefill(plan, li, "wo", attn,
+                                      attn @ layer["wo"].t())
             self._maybe_allreduce(proj)
             hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
                                            residual=residual,
                                            eps=cfg.rms_eps)
-            gu = hidden @ layer["wgu"].t()
+            gu = self._lora_prefill(plan, li, "wgu", hidden,
+                                    hidden @ layer["wgu"].t())
             act = ops.swiglu_fused(gu.contiguous())
-            down = act @ layer["wdown"].t()
+            down = self._lora_prefill(plan, li, "wdown", act,
+                                      act @ layer["wdown"].t())
             self._maybe_allreduce(down)
             next_norm = w.layers[li + 1]["attn_norm"] \
                 if li + 1 < cfg.num_layers else w.final_norm
@@ -688,7 +929,8 @@ class LlamaDecodeEngine:
         return logits
 
     @torch.no_grad()
-    def prefill_packed(self, prompts, slots, starts=None) -> torch.Tensor:
+    def prefill_packed(self, prompts, slots, starts=None, adapters=None
+                       ) -> torch.Tensor:
         """Varlen admission: prefill n prompts of ANY lengths in one
         pass over their concatenated (packed) token stream.  Attention
         is causal within each sequence only (``ops.attn_prefill``) and
@@ -700,7 +942,8 @@ class LlamaDecodeEngine:
         in slot i: the chunk is written at positions starts[i].. and
         attends to that prefix as well (prefix continuation).  Returns
         last-token logits [n, vocab]; sets cache_lens and buf_tokens
-        for the slots like ``prefill_slots``.  bf16 KV caches only."""
+        for the slots like ``prefill_slots``.  bf16 KV caches only.
+        ``adapters``: one LoRA table slot per prompt (-1 = base)."""
         cfg, w = self.cfg, self.weights
         if self.kv_dtype == "fp8":
             raise ValueError("packed prefill needs a bf16 KV cache")
@@ -750,26 +993,31 @@ class LlamaDecodeEngine:
         tokens = torch.tensor([t for p in prompts for t in p],
                               dtype=torch.int64).to(self.device)
         max_q_len = max(lens)
+        plan = self._adapter_plan(adapters, slots_i32.long(), lens)
         x = w.embed[tokens]  # [T, H]
         residual = x.contiguous()
         hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
                              eps=cfg.rms_eps)
         for li, layer in enumerate(w.layers):
-            qkv = hidden @ layer["wqkv"].t()
+            qkv = self._lora_prefill(plan, li, "wqkv", hidden,
+                                     hidden @ layer["wqkv"].t())
             ops.rope_kv_varlen(qkv, self.k_cache[li], self.v_cache[li],
                                positions, tok_slot, self.cos_sin, w.hq)
             q = qkv[:, :w.hq * d].view(T, w.hq, d)  # strided view
             attn = ops.attn_prefill(q, self.k_cache[li], self.v_cache[li],
                                     cu_seqlens, slots_i32, kv_start,
                                     self.scale, max_q_len=max_q_len)
-            proj = attn @ layer["wo"].t()
+            proj = self._lora_prefill(plan, li, "wo", attn,
+                                      attn @ layer["wo"].t())
             self._maybe_allreduce(proj)
             hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
                                            residual=residual,
                                            eps=cfg.rms_eps)
-            gu = hidden @ layer["wgu"].t()
+            gu = self._lora_prefill(plan, li, "wgu", hidden,
+                                    hidden @ layer["wgu"].t())
             act = ops.swiglu_fused(gu.contiguous())
-            down = act @ layer["wdown"].t()
+            down = self._lora_prefill(plan, li, "wdown", act,
+                                      act @ layer["wdown"].t())
             self._maybe_allreduce(down)
             next_norm = w.layers[li + 1]["attn_norm"] \
                 if li + 1 < cfg.num_layers else w.final_norm
@@ -792,13 +1040,14 @@ class LlamaDecodeEngine:
 
     # -------------------------------------------------------- generate
     @torch.no_grad()
-    def generate(self, tokens: torch.Tensor, max_new_tokens: int = 32
-                 ) -> torch.Tensor:
-        """Greedy generation.  tokens [B, S] -> [B, max_new_tokens]."""
+    def generate(self, tokens: torch.Tensor, max_new_tokens: int = 32,
+                 adapters=None) -> torch.Tensor:
+        """Greedy generation.  tokens [B, S] -> [B, max_new_tokens].
+        ``adapters``: one LoRA table slot per row (-1 = base)."""
         B, S = tokens.shape
         assert B == self.B, f"engine built for batch {self.B}, got {B}"
         assert S + max_new_tokens <= self.cfg.max_seq_len
-        logits = self.prefill(tokens)
+        logits = self.prefill(tokens, adapters=adapters)
         next_tokens = self._select_tokens(logits)
         self.buf_tokens.copy_(next_tokens)
         generated = [next_tokens.clone()]
@@ -812,6 +1061,11 @@ class LlamaDecodeEngine:
     # ----------------------------------------------------- speculative
     def _check_speculative(self, k: int):
         """Host-side preconditions of the verify path (no device work)."""
+        if self.lora is not None:
+            raise ValueError(
+                f"speculative decoding conflicts with max_adapters="
+                f"{self.max_adapters}: the verify pass runs the base "
+                "weights only")
         if self.temperature > 0.0 or self.per_slot_temp:
             raise ValueError(
                 "speculative decoding is greedy only (temperature "
@@ -1044,6 +1298,13 @@ class LlamaServer:
       drafts k tokens per step and one verify pass keeps those that
       greedy decoding would have produced (greedy, bf16 weights and KV,
       ``scheduling="batch"`` only; default 0 = off)
+    - ``adapters``: {name: model uri or state file} of LoRA adapters,
+      loaded into table slots shared by all replicas; a request selects
+      one with ``"adapter": name`` (absent / null = base model) and one
+      engine pass — one captured graph — serves rows of different
+      adapters.  ``max_adapters`` (default: their number) sizes the
+      tables, ``lora_rank`` (8/16/32/64) is the table rank.  Not with
+      ``speculative > 0``.  Adapters are fixed once ``load()`` ran.
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -1053,7 +1314,8 @@ class LlamaServer:
                  scheduling="batch", stop_token: int = None,
                  temperature: float = 0.0, top_k: int = 0,
                  prefill: str = "exact", speculative: int = 0,
-                 **class_args):
+                 adapters: dict = None, max_adapters: int = None,
+                 lora_rank: int = 16, **class_args):
         import queue as queue_mod
         import threading
 
@@ -1089,6 +1351,20 @@ class LlamaServer:
         # speculative=k > 0: batch scheduling drafts k tokens per step
         # by n-gram lookup and verifies them in one pass (greedy, bf16)
         self.speculative = int(speculative)
+        # multi-LoRA: {name: model uri or state file}; a request picks
+        # one with "adapter": name.  Table slot = position in the dict.
+        self.adapters = dict(adapters or {})
+        self.adapter_slots = {name: slot for slot, name
+                              in enumerate(self.adapters)}
+        self.max_adapters = len(self.adapters) if max_adapters is None \
+            else int(max_adapters)
+        if self.max_adapters < len(self.adapters):
+            raise ValueError(
+                f"max_adapters={self.max_adapters} is below the "
+                f"{len(self.adapters)} adapters configured")
+        self.lora_rank = int(lora_rank)
+        self._lora_requests = {name: 0 for name in self.adapters}
+        self._lora_lock = threading.Lock()
         self._check_speculative_config()
         self.replicas = max(int(replicas), 1)
         self.engines: typing.List[LlamaDecodeEngine] = []
@@ -1110,6 +1386,11 @@ class LlamaServer:
         k = self.speculative
         if k == 0:
             return
+        if self.max_adapters > 0:
+            raise ValueError(
+                f"speculative={k} conflicts with LoRA adapters "
+                f"({sorted(self.adapters)}): the verify pass runs the "
+                "base weights only")
         if not 1 <= k <= ops.VERIFY_MAX_QL - 1:
             raise ValueError(
                 f"speculative={k} is outside [0, {ops.VERIFY_MAX_QL - 1}]")
@@ -1175,14 +1456,17 @@ class LlamaServer:
                                   weight_dtype=self.weight_dtype,
                                   kv_dtype=self.kv_dtype,
                                   temperature=self.temperature,
-                                  top_k=self.top_k)
+                                  top_k=self.top_k,
+                                  max_adapters=self.max_adapters,
+                                  lora_rank=self.lora_rank)
         self.engines = [first]
         for _ in range(self.replicas - 1):
             replica = LlamaDecodeEngine(
                 cfg, self.batch_size, device=self.device,
                 use_graph=self.use_graph, weights=first.weights,
                 weight_dtype="bf16", kv_dtype=self.kv_dtype,
-                temperature=self.temperature, top_k=self.top_k)
+                temperature=self.temperature, top_k=self.top_k,
+                lora=first.lora)
             replica.weight_dtype = first.weight_dtype
             replica._fp8_packs = first._fp8_packs  # shared packs
             if first.weight_dtype == "fp8w" and replica.on_gpu:
@@ -1207,6 +1491,14 @@ class LlamaServer:
             self.model_spec = spec     # stale (fp8w + model_path)
             for replica in self.engines[1:]:
                 replica._fp8_packs = first._fp8_packs
+        # adapters go into the shared table slots before any capture
+        for name, path in self.adapters.items():
+            from ..artifacts import get_model
+
+            adapter_file, _, _ = get_model(path)
+            state = torch.load(adapter_file, map_location="cpu",
+                               weights_only=True)
+            first.load_adapter(self.adapter_slots[name], state)
         for idx, engine in enumerate(self.engines):
             engine._serve_stream = torch.cuda.Stream() \
                 if engine.on_gpu else None
@@ -1249,21 +1541,24 @@ class LlamaServer:
             item = self._tasks.get()
             if item is None:
                 return
-            prompts, max_new, future = item
+            prompts, max_new, future = item[:3]
+            ids = item[3] if len(item) > 3 else None  # adapter slots
             try:
                 if engine._serve_stream is not None:
                     with torch.cuda.stream(engine._serve_stream):
                         result = self._generate_on(engine, prompts,
-                                                   max_new)
+                                                   max_new, ids)
                     engine._serve_stream.synchronize()
                 else:
-                    result = self._generate_on(engine, prompts, max_new)
+                    result = self._generate_on(engine, prompts, max_new,
+                                               ids)
                 future.set_result(result)
             except Exception as exc:
                 if not future.done():
                     future.set_exception(exc)
 
-    def _stream_generate(self, inputs, max_new, event, req_temp=None):
+    def _stream_generate(self, inputs, max_new, event, req_temp=None,
+                         adapter_id=-1):
         """Token streaming (continuous scheduling only): yields one
         json line per generated token as the slots produce them."""
         import concurrent.futures
@@ -1275,7 +1570,7 @@ class LlamaServer:
             future = concurrent.futures.Future()
             stream_q: "queue_mod.Queue" = queue_mod.Queue()
             self._tasks.put((prompt, max_new, future, stream_q,
-                             req_temp))
+                             req_temp, adapter_id))
             streams.append(stream_q)
 
         def gen():
@@ -1303,7 +1598,7 @@ class LlamaServer:
         admitted at token boundaries via ``prefill_slots`` — no
         generate-pass barrier (vLLM-style scheduling on the fixed-B
         hipGraph).  Each request is one queue item (prompt, max_new,
-        future)."""
+        future[, stream queue[, temperature[, adapter slot]]])."""
         import contextlib
         import queue as queue_mod
 
@@ -1344,11 +1639,12 @@ class LlamaServer:
                         break
             if taken:
                 self.engine_calls += 1
-                prompts, admit_slots = [], []
+                prompts, admit_slots, admit_ids = [], [], []
                 for item, slot in zip(taken, free):
                     prompt, max_new, future = item[:3]
                     stream_q = item[3] if len(item) > 3 else None
                     temp = item[4] if len(item) > 4 else None
+                    admit_ids.append(item[5] if len(item) > 5 else -1)
                     if engine.per_slot_temp:
                         engine.buf_temp[slot] = max(
                             float(temp or 0.0), 1e-4)
@@ -1366,9 +1662,11 @@ class LlamaServer:
                 # output depend on co-arriving traffic (pad tokens are
                 # attended) — measured by the scheduler property test
                 by_len: dict = {}
-                for prompt, slot in zip(prompts, admit_slots):
+                for prompt, slot, aid in zip(prompts, admit_slots,
+                                             admit_ids):
                     by_len.setdefault(len(prompt), []).append(
-                        (prompt, slot))
+                        (prompt, slot, aid))
+                lora_on = engine.lora is not None
                 try:
                     if self.prefill == "packed":
                         # the whole mixed-length group in ONE pass:
@@ -1378,16 +1676,25 @@ class LlamaServer:
                         slot_ids = torch.tensor(admit_slots,
                                                 dtype=torch.long)
                         with stream_ctx():
-                            engine.prefill_packed(prompts, admit_slots)
+                            if lora_on:
+                                engine.prefill_packed(prompts, admit_slots,
+                                                      adapters=admit_ids)
+                            else:
+                                engine.prefill_packed(prompts, admit_slots)
                             out_ring[slot_ids, step % ring_len] = \
                                 engine.buf_tokens[slot_ids]
                     for length, group in by_len.items():
                         tokens = torch.tensor(
-                            [p for p, _ in group], dtype=torch.int64)
+                            [g[0] for g in group], dtype=torch.int64)
                         slot_ids = torch.tensor(
-                            [sl for _, sl in group], dtype=torch.long)
+                            [g[1] for g in group], dtype=torch.long)
                         with stream_ctx():
-                            engine.prefill_slots(tokens, slot_ids)
+                            if lora_on:
+                                engine.prefill_slots(
+                                    tokens, slot_ids,
+                                    adapters=[g[2] for g in group])
+                            else:
+                                engine.prefill_slots(tokens, slot_ids)
                             out_ring[slot_ids, step % ring_len] = \
                                 engine.buf_tokens[slot_ids]
                 except Exception as exc:  # admission failed: fail the
@@ -1474,6 +1781,12 @@ class LlamaServer:
                     if state["stream"]:
                         state["stream"].put(None)  # end-of-stream
                     slots[i] = None
+                if engine.lora is not None:
+                    # freed slots keep stepping: back to the base model,
+                    # so they stop paying for an adapter nobody reads
+                    with stream_ctx():
+                        engine.buf_adapter[torch.tensor(
+                            finished, dtype=torch.long)] = -1
 
     def do_event(self, event):
         import concurrent.futures
@@ -1490,26 +1803,28 @@ class LlamaServer:
             raise ValueError('expected {"inputs": [[token ids], ...]}')
         max_new = int(body.get("max_tokens", self.max_new_tokens))
         req_temp = body.get("temperature")
+        adapter_id = self._adapter_slot(body.get("adapter"))
         if self.scheduling == "continuous" and body.get("stream"):
             event.body = self._stream_generate(inputs, max_new, event,
-                                               req_temp)
+                                               req_temp, adapter_id)
             return event
         if self.scheduling == "continuous":
             futures = []
             for prompt in inputs:
                 future = concurrent.futures.Future()
                 self._tasks.put((prompt, max_new, future, None,
-                                 req_temp))
+                                 req_temp, adapter_id))
                 futures.append(future)
             outputs = [f.result(timeout=600) for f in futures]
         elif self.batch_window_ms and len(inputs) < self.batch_size:
-            outputs = self._batched_submit(inputs, max_new)
+            outputs = self._batched_submit(inputs, max_new, adapter_id)
         else:
             futures = []
             for chunk_start in range(0, len(inputs), self.batch_size):
                 chunk = inputs[chunk_start:chunk_start + self.batch_size]
                 future = concurrent.futures.Future()
-                self._tasks.put((chunk, max_new, future))
+                self._tasks.put((chunk, max_new, future,
+                                 [adapter_id] * len(chunk)))
                 futures.append(future)
             outputs = []
             for future in futures:
@@ -1523,7 +1838,22 @@ class LlamaServer:
                                     event.body)
         return event
 
-    def _batched_submit(self, inputs: list, max_new: int) -> list:
+    def _adapter_slot(self, name) -> int:
+        """Table slot of a request's "adapter" field; absent or null
+        selects the base model (-1).  An unknown name fails the request
+        that carries it, nothing else."""
+        if name is None:
+            return -1
+        if name not in self.adapter_slots:
+            raise ValueError(
+                f"unknown adapter {name!r}; loaded adapters: "
+                f"{sorted(self.adapter_slots)}")
+        with self._lora_lock:
+            self._lora_requests[name] += 1
+        return self.adapter_slots[name]
+
+    def _batched_submit(self, inputs: list, max_new: int,
+                        adapter_id: int = -1) -> list:
         """Queue small requests; the batcher gathers up to batch_size
         prompts within batch_window_ms and submits ONE engine task."""
         import concurrent.futures
@@ -1538,7 +1868,8 @@ class LlamaServer:
                 self._batcher.start()
             for prompt in inputs:
                 future = concurrent.futures.Future()
-                self._pending.append((prompt, max_new, future))
+                self._pending.append((prompt, max_new, future,
+                                      adapter_id))
                 futures.append(future)
             self._pending_cv.notify()
         return [f.result(timeout=600) for f in futures]
@@ -1563,18 +1894,20 @@ class LlamaServer:
             prompts = [b[0] for b in batch]
             max_new = max(b[1] for b in batch)
             task_future = concurrent.futures.Future()
-            self._tasks.put((prompts, max_new, task_future))
+            # one engine pass may mix adapters: one id per prompt
+            ids = [b[3] if len(b) > 3 else -1 for b in batch]
+            self._tasks.put((prompts, max_new, task_future, ids))
             try:
                 results = task_future.result(timeout=600)
-                for (prompt, want, future), result in zip(batch, results):
-                    future.set_result(result[:want])
+                for entry, result in zip(batch, results):
+                    entry[2].set_result(result[:entry[1]])
             except Exception as exc:
-                for _, _, future in batch:
-                    if not future.done():
-                        future.set_exception(exc)
+                for entry in batch:
+                    if not entry[2].done():
+                        entry[2].set_exception(exc)
 
     def _generate_on(self, engine: LlamaDecodeEngine, prompts: list,
-                     max_new: int) -> list:
+                     max_new: int, adapters: list = None) -> list:
         """Batch generation with per-LENGTH prefill groups: padding a
         mixed-length batch would let pad tokens be attended, making a
         prompt's output depend on its co-batch (see the continuous
@@ -1585,11 +1918,18 @@ class LlamaServer:
         for i, prompt in enumerate(prompts):
             by_len.setdefault(len(prompt), []).append(i)
         engine.reset()
+        lora_on = engine.lora is not None
+        if lora_on:
+            engine.buf_adapter.fill_(-1)  # rows beyond n run the base
         for length, idxs in by_len.items():
             tokens = torch.tensor([prompts[i] for i in idxs],
                                   dtype=torch.int64)
-            engine.prefill_slots(tokens, torch.tensor(idxs,
-                                                      dtype=torch.long))
+            slot_ids = torch.tensor(idxs, dtype=torch.long)
+            if lora_on and adapters is not None:
+                engine.prefill_slots(tokens, slot_ids,
+                                     adapters=[adapters[i] for i in idxs])
+            else:
+                engine.prefill_slots(tokens, slot_ids)
         if self.speculative > 0:
             out = self._speculate_on(engine, prompts, max_new)
         else:
@@ -1643,6 +1983,11 @@ class LlamaServer:
         return request.get("inputs"), None
 
     def stats(self):
+        if self.adapters:
+            with self._lora_lock:
+                counts = dict(self._lora_requests)
+            return {"lora": {"adapters": list(self.adapters),
+                             "requests": counts}}
         if not self.speculative:
             return {}
         totals = {"steps": 0, "drafted": 0, "accepted": 0}

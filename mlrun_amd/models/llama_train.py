@@ -147,16 +147,70 @@ class LlamaForCausalLM(nn.Module):
         return logits, loss
 
 
+LORA_TARGETS = ("wqkv", "wo", "wgu", "wdown")
+
+
+class LoraLinear(nn.Linear):
+    """A frozen nn.Linear plus a trainable low-rank branch:
+    y = x W^T + (alpha / r) (x A^T) B^T.  It keeps the base layer's
+    ``weight`` parameter (and its state-dict key), A starts as a small
+    normal and B as zero, so training starts at the base model."""
+
+    def __init__(self, base: nn.Linear, rank: int, alpha: float):
+        super().__init__(base.in_features, base.out_features, bias=False,
+                         device="meta")
+        self.weight = base.weight
+        kwargs = dict(device=base.weight.device, dtype=base.weight.dtype)
+        self.lora_A = nn.Parameter(
+            torch.empty(rank, base.in_features, **kwargs).normal_(0, 0.01))
+        self.lora_B = nn.Parameter(
+            torch.zeros(base.out_features, rank, **kwargs))
+        self.rank = rank
+        self.alpha = float(alpha)
+
+    def forward(self, x):
+        low = F.linear(F.linear(x, self.lora_A), self.lora_B)
+        return F.linear(x, self.weight) + low * (self.alpha / self.rank)
+
+
+def _lora_modules(model: "LlamaForCausalLM"):
+    """(layer index, projection name, owner module) of every nn.Linear
+    a LoRA branch can attach to."""
+    for i, block in enumerate(model.blocks):
+        yield i, "wqkv", block.attn
+        yield i, "wo", block.attn
+        yield i, "wgu", block.mlp
+        yield i, "wdown", block.mlp
+
+
 class LlamaTrainer:
     """The config-4 training loop: DDP over RCCL/xGMI, synthetic data,
-    tokens/s accounting, artifact checkpointing."""
+    tokens/s accounting, artifact checkpointing.
+
+    ``lora_rank > 0`` turns it into a LoRA fine-tune: the base
+    parameters are frozen, the ``lora_targets`` projections get a
+    rank-r branch (``lora_alpha`` defaults to 2 r) and the optimizer
+    sees the adapter parameters only.  ``save_adapter`` logs the result
+    in the format ``LlamaDecodeEngine.load_adapter`` reads.  Single
+    process only."""
 
     def __init__(self, cfg: LlamaConfig, device=None, lr: float = 1e-4,
                  bucket_cap_mb: int = None, context=None,
                  grad_accum_steps: int = 1, warmup_steps: int = 0,
                  total_steps: int = 0, min_lr_ratio: float = 0.1,
-                 grad_clip: float = 1.0):
+                 grad_clip: float = 1.0, lora_rank: int = 0,
+                 lora_alpha: float = None, lora_targets=LORA_TARGETS):
         self.cfg = cfg
+        self.lora_rank = int(lora_rank)
+        self.lora_alpha = float(
+            2 * self.lora_rank if lora_alpha is None else lora_alpha)
+        self.lora_targets = tuple(lora_targets)
+        if self.lora_rank < 0:
+            raise ValueError(f"lora_rank must be >= 0, got {lora_rank}")
+        unknown = set(self.lora_targets) - set(LORA_TARGETS)
+        if unknown:
+            raise ValueError(f"unknown lora_targets {sorted(unknown)} "
+                             f"(expected a subset of {LORA_TARGETS})")
         self.grad_accum_steps = max(int(grad_accum_steps), 1)
         self.warmup_steps = warmup_steps
         self.total_steps = total_steps
@@ -176,6 +230,14 @@ class LlamaTrainer:
         self.world_size = dist.get_world_size() if dist.is_initialized() \
             else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
+        if self.lora_rank > 0:
+            if self.world_size > 1:
+                raise ValueError(
+                    f"lora_rank={self.lora_rank} with world_size="
+                    f"{self.world_size}: LoRA fine-tuning runs in a "
+                    "single process (data-parallel training with "
+                    "frozen base parameters is not covered)")
+            self._attach_lora()
         if self.world_size > 1:
             from ..parallel.ddp import DistributedModel
 
@@ -183,9 +245,53 @@ class LlamaTrainer:
                                         bucket_cap_mb=bucket_cap_mb)
         else:
             self.ddp = None
-        self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=lr,
+        params = [p for p in self.model.parameters() if p.requires_grad]
+        self.optimizer = torch.optim.AdamW(params, lr=lr,
                                            betas=(0.9, 0.95),
                                            weight_decay=0.1, foreach=True)
+
+    def _attach_lora(self):
+        """Freeze the base model and put a LoraLinear in place of every
+        targeted projection."""
+        for param in self.model.parameters():
+            param.requires_grad_(False)
+        for _, proj, owner in _lora_modules(self.model):
+            if proj in self.lora_targets:
+                setattr(owner, proj, LoraLinear(
+                    getattr(owner, proj), self.lora_rank, self.lora_alpha))
+
+    def adapter_state(self) -> dict:
+        """The trained adapter as ``LlamaDecodeEngine.load_adapter``
+        reads it: ``layers.{i}.{proj}.lora_A`` [r, K] and ``.lora_B``
+        [N, r] (CPU copies) plus ``alpha`` and ``rank``."""
+        if self.lora_rank <= 0:
+            raise ValueError("adapter_state needs lora_rank > 0")
+        state = {"alpha": self.lora_alpha, "rank": self.lora_rank}
+        for i, proj, owner in _lora_modules(self.model):
+            module = getattr(owner, proj)
+            if isinstance(module, LoraLinear):
+                prefix = f"layers.{i}.{proj}."
+                state[prefix + "lora_A"] = \
+                    module.lora_A.detach().cpu().clone()
+                state[prefix + "lora_B"] = \
+                    module.lora_B.detach().cpu().clone()
+        return state
+
+    def save_adapter(self, key: str = "adapter"):
+        """Log the adapter alone as a model artifact (rank 0 only, like
+        save_checkpoint): tens of MB instead of a copy of the weights.
+        ``LlamaServer(adapters={name: uri})`` serves it."""
+        if self.rank != 0 or self.context is None:
+            return None
+        import io
+
+        buf = io.BytesIO()
+        torch.save(self.adapter_state(), buf)
+        return self.context.log_model(
+            key, body=buf.getvalue(), framework="pytorch",
+            parameters={"kind": "lora", "rank": self.lora_rank,
+                        "alpha": self.lora_alpha,
+                        "config": self.cfg.name})
 
     def current_lr(self) -> float:
         """Linear warmup + cosine decay to min_lr_ratio (standard

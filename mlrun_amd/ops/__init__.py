@@ -651,6 +651,94 @@ def ngram_draft(history: torch.Tensor, hist_lens: torch.Tensor, k: int,
     return out
 
 
+# ------------------------------------------------------------ multi-LoRA
+
+LORA_RANKS = (8, 16, 32, 64)   # table ranks the kernels are built for
+LORA_MAX_ROWS = 64             # decode rows per launch
+
+
+def _check_lora(rows, t, table, idx, width_name):
+    """Shared argument checks of lora_shrink / lora_expand: rows is the
+    bf16 [B, width] activation (x or y), table the [NA, ., .] bf16
+    adapter table, t the f32 [B, R] intermediate."""
+    for name, tensor, dtype in (("rows", rows, torch.bfloat16),
+                                ("table", table, torch.bfloat16),
+                                ("t", t, torch.float32),
+                                ("idx", idx, torch.int32)):
+        if tensor.dtype != dtype:
+            raise ValueError(f"lora: {name} must be {dtype}, got "
+                             f"{tensor.dtype}")
+        if not tensor.is_contiguous():
+            raise ValueError(f"lora: {name} must be contiguous")
+    if rows.dim() != 2 or t.dim() != 2 or table.dim() != 3 or \
+            idx.dim() != 1:
+        raise ValueError("lora: expected rows [B, width], t [B, R], a "
+                         "3-d table and idx [B]")
+    B, width = rows.shape
+    R = t.shape[1]
+    if B > LORA_MAX_ROWS:
+        raise ValueError(f"lora: B must be <= {LORA_MAX_ROWS}, got {B}")
+    if t.shape[0] != B or idx.numel() != B:
+        raise ValueError("lora: rows, t and idx must agree on B")
+    if R not in LORA_RANKS:
+        raise ValueError(f"lora: R must be one of {LORA_RANKS}, got {R}")
+    if width % 8:
+        raise ValueError(f"lora: {width_name} must be a multiple of 8, "
+                         f"got {width}")
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, idx: torch.Tensor,
+                out: torch.Tensor = None) -> torch.Tensor:
+    """Multi-LoRA shrink for a decode batch: row b uses adapter idx[b],
+    t[b, j] = sum_k x[b, k] * A[idx[b], j, k] with f32 accumulation.
+
+    x [B, K] bf16 (B <= 64, K % 8 == 0), A [NA, R, K] bf16 with R in
+    {8, 16, 32, 64}, idx [B] int32.  Returns t [B, R] f32 (``out`` when
+    given).  Rows whose id is outside [0, NA) are skipped: their t row
+    is left as it was.  Bad shapes, dtypes or layouts raise ValueError."""
+    if A.dim() != 3:
+        raise ValueError("lora_shrink: A must be [NA, R, K]")
+    if out is None:
+        out = torch.zeros(x.shape[0], A.shape[1], dtype=torch.float32,
+                          device=x.device)
+    _check_lora(x, out, A, idx, "K")
+    if A.shape[1] != out.shape[1] or A.shape[2] != x.shape[1]:
+        raise ValueError("lora_shrink: A must be [NA, R, K] matching "
+                         "x [B, K] and t [B, R]")
+    if x.is_cuda:
+        _require_hip().lora_shrink(out, x, A, idx)
+        return out
+    NA = A.shape[0]
+    for b, a in enumerate(idx.tolist()):
+        if 0 <= a < NA:
+            out[b] = A[a].float() @ x[b].float()
+    return out
+
+
+def lora_expand(y: torch.Tensor, t: torch.Tensor, Bm: torch.Tensor,
+                idx: torch.Tensor) -> torch.Tensor:
+    """Multi-LoRA expand, in place: y[b, n] = bf16(float(y[b, n]) +
+    sum_j t[b, j] * Bm[idx[b], n, j]) — f32 accumulation, one rounding.
+
+    y [B, N] bf16 (B <= 64, N % 8 == 0), t [B, R] f32, Bm [NA, N, R]
+    bf16 (alpha / r already folded in), idx [B] int32.  Rows whose id
+    is outside [0, NA) are left untouched.  Returns y."""
+    if Bm.dim() != 3:
+        raise ValueError("lora_expand: Bm must be [NA, N, R]")
+    _check_lora(y, t, Bm, idx, "N")
+    if Bm.shape[1] != y.shape[1] or Bm.shape[2] != t.shape[1]:
+        raise ValueError("lora_expand: Bm must be [NA, N, R] matching "
+                         "y [B, N] and t [B, R]")
+    if y.is_cuda:
+        _require_hip().lora_expand(y, t, Bm, idx)
+        return y
+    NA = Bm.shape[0]
+    for b, a in enumerate(idx.tolist()):
+        if 0 <= a < NA:
+            y[b] = (y[b].float() + Bm[a].float() @ t[b]).to(y.dtype)
+    return y
+
+
 def kv_append(k_cache, v_cache, k_new, v_new, positions):
     """Scatter the new token K/V into the cache at positions[b]."""
     if k_cache.is_cuda:

@@ -489,6 +489,56 @@ void ngram_draft(torch::Tensor drafts, torch::Tensor history,
                      stream());
 }
 
+// multi-LoRA decode (BGMV): shared shape checks of the two kernels
+static void check_lora(const torch::Tensor& act, const torch::Tensor& t,
+                       const torch::Tensor& table, const torch::Tensor& idx,
+                       int64_t width, const char* width_name) {
+  TORCH_CHECK(act.dim() == 2 && t.dim() == 2 && table.dim() == 3 &&
+              idx.dim() == 1, "lora: expected 2-d rows, t [B, R], a "
+              "[NA, ., .] table and idx [B]");
+  int64_t B = act.size(0), R = t.size(1);
+  TORCH_CHECK(B <= 64, "lora: at most 64 rows, got ", B);
+  TORCH_CHECK(t.size(0) == B && idx.numel() == B,
+              "lora: rows, t and idx must agree on B");
+  TORCH_CHECK(R == 8 || R == 16 || R == 32 || R == 64,
+              "lora: rank must be 8, 16, 32 or 64, got ", R);
+  TORCH_CHECK(width % 8 == 0, "lora: ", width_name,
+              " must be a multiple of 8, got ", width);
+  TORCH_CHECK(table.size(0) < (1LL << 20) && width < (1LL << 24),
+              "lora: shape too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(act.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0,
+              "lora: rows and tables must be 16-byte aligned");
+}
+
+void lora_shrink(torch::Tensor t, torch::Tensor x, torch::Tensor A,
+                 torch::Tensor idx) {
+  CHECK_DEV(t); CHECK_CONTIG(t); CHECK_F32(t);
+  CHECK_DEV(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_DEV(A); CHECK_CONTIG(A); CHECK_BF16(A);
+  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_I32(idx);
+  check_lora(x, t, A, idx, x.dim() == 2 ? x.size(1) : 0, "K");
+  TORCH_CHECK(A.size(1) == t.size(1) && A.size(2) == x.size(1),
+              "lora_shrink: A must be [NA, R, K]");
+  launch_lora_shrink(t.data_ptr(), x.data_ptr(), A.data_ptr(),
+                     idx.data_ptr(), (int)x.size(0), (int)A.size(0),
+                     (int)t.size(1), (int)x.size(1), stream());
+}
+
+void lora_expand(torch::Tensor y, torch::Tensor t, torch::Tensor Bm,
+                 torch::Tensor idx) {
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y);
+  CHECK_DEV(t); CHECK_CONTIG(t); CHECK_F32(t);
+  CHECK_DEV(Bm); CHECK_CONTIG(Bm); CHECK_BF16(Bm);
+  CHECK_DEV(idx); CHECK_CONTIG(idx); CHECK_I32(idx);
+  check_lora(y, t, Bm, idx, y.dim() == 2 ? y.size(1) : 0, "N");
+  TORCH_CHECK(Bm.size(1) == y.size(1) && Bm.size(2) == t.size(1),
+              "lora_expand: Bm must be [NA, N, R]");
+  launch_lora_expand(y.data_ptr(), t.data_ptr(), Bm.data_ptr(),
+                     idx.data_ptr(), (int)y.size(0), (int)Bm.size(0),
+                     (int)t.size(1), (int)y.size(1), stream());
+}
+
 void softmax(torch::Tensor out, torch::Tensor in) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(in); CHECK_CONTIG(in); CHECK_BF16(in);
@@ -648,6 +698,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ngram_draft", &ngram_draft, py::arg("drafts"), py::arg("history"),
         py::arg("hist_lens"), py::arg("n"),
         "device-side prompt-lookup (n-gram) drafter");
+  m.def("lora_shrink", &lora_shrink, py::arg("t"), py::arg("x"),
+        py::arg("a"), py::arg("idx"),
+        "multi-LoRA shrink: t[b] = A[idx[b]] @ x[b] (f32)");
+  m.def("lora_expand", &lora_expand, py::arg("y"), py::arg("t"),
+        py::arg("bm"), py::arg("idx"),
+        "multi-LoRA expand: y[b] += Bm[idx[b]] @ t[b], in place (bf16)");
   m.def("softmax", &softmax, "row softmax (bf16)");
   m.def("tree_ensemble", &tree_ensemble, "GBDT ensemble inference (f32)");
   m.def("window_ingest", &window_ingest,

@@ -102,6 +102,14 @@ void launch_ngram_draft(void* drafts, const void* history,
                         const void* hist_lens, int B, int L, int k, int n,
                         void* stream);
 
+void launch_lora_shrink(void* t, const void* x, const void* A,
+                        const void* idx, int B, int NA, int R, int K,
+                        void* stream);
+
+void launch_lora_expand(void* y, const void* t, const void* Bm,
+                        const void* idx, int B, int NA, int R, int N,
+                        void* stream);
+
 void launch_softmax(void* out, const void* in, int rows, int cols,
                     void* stream);
 

@@ -2481,6 +2481,121 @@ void launch_ngram_draft(void* drafts, const void* history,
 }
 
 // ---------------------------------------------------------------------
+// Multi-LoRA decode: batched gather mat-vec (BGMV) pair.  Row b of a
+// decode batch uses adapter idx[b] of the tables A [NA, R, K] and
+// Bm [NA, N, R] (bf16; alpha / r is folded into Bm at load time):
+//   shrink: t[b, j] = sum_k x[b, k] * A[idx[b], j, k]           (f32)
+//   expand: y[b, n] = bf16(float(y[b, n]) + sum_j t[b, j] * Bm[idx[b], n, j])
+// idx is read on the device, so a captured graph follows whatever ids
+// the host wrote last.  A row whose id is outside [0, NA) is skipped:
+// its workgroup returns before any barrier (the test is block-uniform)
+// and touches neither t nor y.
+// ---------------------------------------------------------------------
+#define LORA_SHRINK_THREADS 256
+#define LORA_EXPAND_THREADS 128
+#define LORA_EXPAND_TILE (2 * LORA_EXPAND_THREADS)  // n per workgroup
+
+// One workgroup per (j, b): its 256 lanes sweep K in 16 B pieces, then
+// wave shuffles and a 4-entry LDS fold give one f32 in a fixed order.
+__global__ __launch_bounds__(LORA_SHRINK_THREADS) void lora_shrink_kernel(
+    float* __restrict__ t, const unsigned short* __restrict__ x,
+    const unsigned short* __restrict__ A, const int* __restrict__ idx,
+    int NA, int R, int K) {
+  __shared__ float wave_sum[LORA_SHRINK_THREADS / 64];
+  const int j = blockIdx.x;
+  const int b = blockIdx.y;
+  const int a = idx[b];
+  if (a < 0 || a >= NA) return;
+  const int tid = threadIdx.x;
+  const unsigned short* xr = x + (size_t)b * K;
+  const unsigned short* ar = A + ((size_t)a * R + j) * K;
+  float acc = 0.f;
+#pragma unroll 4
+  for (int k = tid * 8; k < K; k += LORA_SHRINK_THREADS * 8) {
+    const short8v xv = *reinterpret_cast<const short8v*>(xr + k);
+    const short8v av = *reinterpret_cast<const short8v*>(ar + k);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      acc += bf2f((unsigned short)xv[i]) * bf2f((unsigned short)av[i]);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((tid & 63) == 0) wave_sum[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0)
+    t[(size_t)b * R + j] =
+        (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+}
+
+// One workgroup per (256-wide n tile, b); a thread owns two adjacent
+// outputs (one dword of y) and reads their two Bm rows, 2 * R bf16 in a
+// row, with 16 B loads.  t[b, :] is staged in LDS.
+template <int R>
+__global__ __launch_bounds__(LORA_EXPAND_THREADS) void lora_expand_kernel(
+    unsigned short* __restrict__ y, const float* __restrict__ t,
+    const unsigned short* __restrict__ Bm, const int* __restrict__ idx,
+    int NA, int N) {
+  __shared__ float ts[R];
+  const int b = blockIdx.y;
+  const int a = idx[b];
+  if (a < 0 || a >= NA) return;
+  const int tid = threadIdx.x;
+  if (tid < R) ts[tid] = t[(size_t)b * R + tid];
+  __syncthreads();
+  const int n = (blockIdx.x * LORA_EXPAND_THREADS + tid) * 2;
+  if (n >= N) return;  // N is even: n + 1 < N as well
+  const unsigned short* rows = Bm + ((size_t)a * N + n) * R;
+  float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+  for (int j = 0; j < R; j += 8) {
+    const short8v r0 = *reinterpret_cast<const short8v*>(rows + j);
+    const short8v r1 = *reinterpret_cast<const short8v*>(rows + R + j);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      acc0 += ts[j + i] * bf2f((unsigned short)r0[i]);
+      acc1 += ts[j + i] * bf2f((unsigned short)r1[i]);
+    }
+  }
+  ushort2v* yp = reinterpret_cast<ushort2v*>(y + (size_t)b * N + n);
+  ushort2v v = *yp;
+  v.x = f2bf(bf2f(v.x) + acc0);
+  v.y = f2bf(bf2f(v.y) + acc1);
+  *yp = v;
+}
+
+void launch_lora_shrink(void* t, const void* x, const void* A,
+                        const void* idx, int B, int NA, int R, int K,
+                        void* stream) {
+  if (B <= 0 || NA <= 0) return;
+  hipLaunchKernelGGL(lora_shrink_kernel, dim3(R, B),
+                     dim3(LORA_SHRINK_THREADS), 0, (hipStream_t)stream,
+                     (float*)t, (const unsigned short*)x,
+                     (const unsigned short*)A, (const int*)idx, NA, R, K);
+}
+
+void launch_lora_expand(void* y, const void* t, const void* Bm,
+                        const void* idx, int B, int NA, int R, int N,
+                        void* stream) {
+  if (B <= 0 || NA <= 0) return;
+  const dim3 grid((N + LORA_EXPAND_TILE - 1) / LORA_EXPAND_TILE, B);
+#define LORA_EXPAND_CASE(RR)                                              \
+  case RR:                                                                \
+    hipLaunchKernelGGL(lora_expand_kernel<RR>, grid,                      \
+                       dim3(LORA_EXPAND_THREADS), 0, (hipStream_t)stream, \
+                       (unsigned short*)y, (const float*)t,               \
+                       (const unsigned short*)Bm, (const int*)idx, NA, N); \
+    break;
+  switch (R) {
+    LORA_EXPAND_CASE(8)
+    LORA_EXPAND_CASE(16)
+    LORA_EXPAND_CASE(32)
+    LORA_EXPAND_CASE(64)
+    default: break;  // the binding rejects other ranks
+  }
+#undef LORA_EXPAND_CASE
+}
+
+// ---------------------------------------------------------------------
 // Row softmax (bf16 in/out, online single pass over LDS-staged row,
 // used by classic-model servers & tests)
 // ---------------------------------------------------------------------
