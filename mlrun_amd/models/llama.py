@@ -153,6 +153,55 @@ def _training_state_to_decode(state: dict) -> dict:
 LORA_PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
 
 
+@dataclass
+class SamplingParams:
+    """How one prompt's tokens are chosen under ``sampling="request"``:
+    the defaults are greedy with every filter off.  ``logprobs`` asks
+    the server to return the chosen tokens' log-probabilities."""
+    temperature: float = 0.0
+    top_k: int = 0
+    top_p: float = 1.0
+    min_p: float = 0.0
+    seed: int = 0
+    logprobs: bool = False
+
+    def validate(self):
+        """ValueError naming the field that is out of range."""
+        def number(name, value):
+            if isinstance(value, bool) or \
+                    not isinstance(value, (int, float)) or \
+                    value != value:
+                raise ValueError(f"{name} must be a number, got {value!r}")
+
+        def integer(name, value):
+            if isinstance(value, bool) or not isinstance(value, int):
+                raise ValueError(f"{name} must be an integer, got "
+                                 f"{value!r}")
+
+        number("temperature", self.temperature)
+        if not 0 <= self.temperature < float("inf"):
+            raise ValueError(f"temperature must be >= 0 and finite, got "
+                             f"{self.temperature}")
+        integer("top_k", self.top_k)
+        if not 0 <= self.top_k < 2 ** 31:
+            raise ValueError(f"top_k must be an integer >= 0, got "
+                             f"{self.top_k}")
+        number("top_p", self.top_p)
+        if not 0 < self.top_p <= 1:
+            raise ValueError(f"top_p must be in (0, 1], got {self.top_p}")
+        number("min_p", self.min_p)
+        if not 0 <= self.min_p < 1:
+            raise ValueError(f"min_p must be in [0, 1), got {self.min_p}")
+        integer("seed", self.seed)
+        if not 0 <= self.seed < 2 ** 63:
+            raise ValueError(f"seed must be an integer in [0, 2^63), got "
+                             f"{self.seed}")
+        if not isinstance(self.logprobs, bool):
+            raise ValueError(f"logprobs must be true or false, got "
+                             f"{self.logprobs!r}")
+        return self
+
+
 class LoraTables:
     """Adapter tables of a multi-LoRA engine: per layer and projection
     ``A [NA, R, K]`` and ``Bm [NA, N, R]`` bf16, zero-initialised and
@@ -263,7 +312,18 @@ class LlamaDecodeEngine:
                  weight_dtype: str = "bf16", kv_dtype: str = "bf16",
                  temperature: float = 0.0, top_k: int = 0,
                  max_adapters: int = 0, lora_rank: int = 16,
-                 lora: "LoraTables" = None):
+                 lora: "LoraTables" = None, sampling: str = "engine"):
+        if sampling not in ("engine", "request"):
+            raise ValueError(f"unknown sampling mode {sampling!r} "
+                             "(expected 'engine' or 'request')")
+        if sampling == "request" and tp_size > 1:
+            raise ValueError(
+                f'sampling="request" conflicts with tp_size={tp_size}: '
+                "per-request sampling runs on a single GPU")
+        if sampling == "request" and batch_size > ops.SAMPLE_MAX_ROWS:
+            raise ValueError(
+                f'sampling="request" needs batch_size <= '
+                f"{ops.SAMPLE_MAX_ROWS}, got {batch_size}")
         if (max_adapters > 0 or lora is not None) and tp_size > 1:
             raise ValueError(
                 f"max_adapters={max_adapters} conflicts with tp_size="
@@ -403,8 +463,98 @@ class LlamaDecodeEngine:
             self.buf_lora_t = torch.zeros(B, lora.rank,
                                           dtype=torch.float32,
                                           device=self.device)
+        # per-request sampling (opt-in): every slot carries its own
+        # parameters in device buffers read by ops.sample_tokens, so one
+        # captured graph serves rows that sample differently.  Defaults:
+        # greedy, filters off.  With sampling == "engine" nothing is
+        # allocated and _select_tokens picks the tokens as before.
+        self.sampling = sampling
+        if sampling == "request":
+            dev = self.device
+            self.buf_temp_r = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.buf_top_k = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.buf_top_p = torch.ones(B, dtype=torch.float32, device=dev)
+            self.buf_min_p = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.buf_seed = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.buf_logprob = torch.zeros(B, dtype=torch.float32,
+                                           device=dev)
+            self.buf_kept = torch.zeros(B, dtype=torch.int32, device=dev)
         # speculative decoding (opt-in): running acceptance counters
         self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
+
+    # -------------------------------------------------------- sampling
+    def set_sampling(self, slot: int, temperature: float = 0.0,
+                     top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
+                     seed: int = 0):
+        """Write one slot's sampling parameters (sampling="request"
+        engines).  The captured graph reads them on the device, so the
+        change holds from the next step on without a recapture."""
+        self.set_sampling_slots([slot], [SamplingParams(
+            temperature, top_k, top_p, min_p, seed)])
+
+    def set_sampling_slots(self, slots, params):
+        """set_sampling for several slots at once: ``params`` holds one
+        SamplingParams (None = the defaults) per slot; one host-to-
+        device copy per parameter.  A temperature in (0, 1e-4) is
+        raised to 1e-4, the floor of the ``temperature=-1`` path: below
+        it the draw is the argmax anyway."""
+        if self.sampling != "request":
+            raise ValueError('set_sampling needs an engine built with '
+                             'sampling="request"')
+        slots = [int(slot) for slot in slots]
+        params = [SamplingParams() if item is None else item
+                  for item in params]
+        if len(slots) != len(params):
+            raise ValueError(f"{len(params)} parameter sets for "
+                             f"{len(slots)} slots")
+        for slot in slots:
+            if not 0 <= slot < self.B:
+                raise ValueError(f"slot {slot} outside [0, {self.B})")
+        for item in params:
+            item.validate()
+        if not slots:
+            return
+        index = torch.tensor(slots, dtype=torch.long).to(self.device)
+        for buf, name in ((self.buf_temp_r, "temperature"),
+                          (self.buf_top_k, "top_k"),
+                          (self.buf_top_p, "top_p"),
+                          (self.buf_min_p, "min_p"),
+                          (self.buf_seed, "seed")):
+            values = [getattr(item, name) for item in params]
+            if name == "temperature":
+                # like buf_temp: z / T stays finite for any real logit
+                values = [max(value, 1e-4) if value > 0 else value
+                          for value in values]
+            values = torch.tensor(values, dtype=buf.dtype)
+            buf[index] = values.to(self.device)
+
+    def _packed_prefill_serves(self) -> bool:
+        """Whether prefill_packed (ops.attn_prefill) handles this
+        engine: bf16 KV, head_dim 128, group size <= 8."""
+        w = self.weights
+        return self.kv_dtype == "bf16" and self.cfg.head_dim == 128 \
+            and w.hq % w.hkv == 0 and w.hq // w.hkv <= 8
+
+    def _sample_slots(self, logits, slots):
+        """First token of freshly prefilled ``slots`` (a long tensor or
+        a slice of rows) from their last-token logits [n, vocab], by
+        each slot's own parameters; pos = the prompt length."""
+        logits = logits.contiguous()
+        n = logits.shape[0]
+        tokens = torch.empty(n, dtype=torch.int64, device=self.device)
+        logprob = torch.empty(n, dtype=torch.float32, device=self.device)
+        kept = torch.empty(n, dtype=torch.int32, device=self.device)
+        ops.sample_tokens(
+            logits, self.cache_lens[slots].contiguous(),
+            self.buf_temp_r[slots].contiguous(),
+            self.buf_top_k[slots].contiguous(),
+            self.buf_top_p[slots].contiguous(),
+            self.buf_min_p[slots].contiguous(),
+            self.buf_seed[slots].contiguous(), tokens, logprob, kept)
+        self.buf_tokens[slots] = tokens
+        self.buf_logprob[slots] = logprob
+        self.buf_kept[slots] = kept
+        return tokens
 
     # ------------------------------------------------------------ gemm
     def _plan(self, w_):
@@ -665,7 +815,15 @@ class LlamaDecodeEngine:
                                       out8=h8, out_scale=h8s)
         self._gemm(self.buf_hidden, w.lm_head, self.buf_logits,
                    a8=h8, a_scale=h8s)
-        self._select_tokens(self.buf_logits, out=self.buf_tokens)
+        if self.sampling == "request":
+            # pos = the bumped length: the position of the new token
+            ops.sample_tokens(self.buf_logits, self.cache_lens,
+                              self.buf_temp_r, self.buf_top_k,
+                              self.buf_top_p, self.buf_min_p, self.buf_seed,
+                              self.buf_tokens, self.buf_logprob,
+                              self.buf_kept)
+        else:
+            self._select_tokens(self.buf_logits, out=self.buf_tokens)
 
     def _select_tokens(self, logits: torch.Tensor,
                        out: torch.Tensor = None) -> torch.Tensor:
@@ -724,6 +882,10 @@ class LlamaDecodeEngine:
 
         lens_backup = self.cache_lens.clone()
         tokens_backup = self.buf_tokens.clone()
+        # the warm-up steps sample too: keep the pending tokens' logprobs
+        sample_backup = [(buf, buf.clone()) for buf in (
+            self.buf_logprob, self.buf_kept)] \
+            if self.sampling == "request" else []
         if self.tp_size > 1 and dist.is_available() and \
                 dist.is_initialized():
             # warmup runs REAL collectives — align ranks first so the
@@ -737,6 +899,8 @@ class LlamaDecodeEngine:
         torch.cuda.current_stream().wait_stream(side)
         self.cache_lens.copy_(lens_backup)
         self.buf_tokens.copy_(tokens_backup)
+        for buf, backup in sample_backup:
+            buf.copy_(backup)
         graph = torch.cuda.CUDAGraph()
         # RCCL collectives ARE capturable (the all-reduce kernel is
         # recorded into the graph and pairs up across ranks at replay),
@@ -752,6 +916,8 @@ class LlamaDecodeEngine:
         # in case a backend executed eagerly during capture
         self.cache_lens.copy_(lens_backup)
         self.buf_tokens.copy_(tokens_backup)
+        for buf, backup in sample_backup:
+            buf.copy_(backup)
         self._graph = graph
         logger.info("decode hipGraph captured", batch=self.B,
                     layers=self.cfg.num_layers)
@@ -785,6 +951,18 @@ class LlamaDecodeEngine:
     def _vscale(self, li):
         return None if self.v_scale is None else self.v_scale[li]
 
+    def _check_token_ids(self, tokens: torch.Tensor):
+        """ValueError for a prompt id outside the vocabulary, checked
+        on the host: on the device the embedding gather would read
+        outside the table, and a fault there ends the whole process.
+        Tokens already on the device are not checked (no sync)."""
+        if tokens.device.type != "cpu" or tokens.numel() == 0:
+            return
+        low, high = int(tokens.min()), int(tokens.max())
+        if low < 0 or high >= self.cfg.vocab_size:
+            raise ValueError(
+                f"token id outside [0, {self.cfg.vocab_size}) in prompt")
+
     @torch.no_grad()
     def prefill(self, tokens: torch.Tensor, adapters=None
                 ) -> torch.Tensor:
@@ -795,6 +973,7 @@ class LlamaDecodeEngine:
         cfg, w = self.cfg, self.weights
         B, S = tokens.shape
         d = cfg.head_dim
+        self._check_token_ids(tokens)
         plan = self._adapter_plan(adapters, slice(0, B), [S] * B)
         tokens = tokens.to(self.device)
         x = w.embed[tokens.reshape(-1)]  # [B*S, H]
@@ -848,6 +1027,8 @@ class LlamaDecodeEngine:
         self.cache_lens.fill_(S)
         last = hidden.view(B, S, -1)[:, -1]
         logits = last @ w.lm_head.t()
+        if self.sampling == "request":
+            self._sample_slots(logits, slice(0, B))
         return logits
 
     @torch.no_grad()
@@ -856,15 +1037,34 @@ class LlamaDecodeEngine:
         """Continuous-batching admission: prefill B' <= B prompts and
         scatter their KV/state into cache rows ``slots``, leaving the
         other slots' caches and lengths untouched.  Returns last-token
-        logits [B'].  (Runs the same prefill math on a temporary
-        B'-sized view; decode then advances ALL slots each step.)
-        ``adapters``: one LoRA table slot per prompt (-1 = base)."""
+        logits [B'].  ``adapters``: one LoRA table slot per prompt
+        (-1 = base).  Decode then advances ALL slots each step.
+
+        Two code paths.  A sampling="engine" engine, and any engine
+        whose shape the packed attention kernel does not serve, runs
+        the same prefill math as ``prefill`` on a temporary B'-sized
+        view.  A sampling="request" engine that the packed kernel
+        serves (bf16 KV, head_dim 128, at most 8 q-heads per KV head)
+        does NOT: it hands the prompts to ``prefill_packed``.  A seeded
+        request must return the same tokens AND logprobs under either
+        prefill mode of the server, which needs one attention code path
+        for both, not two that agree within a bound.  On that path the
+        argument checks are ``prefill_packed``'s, so a slot count that
+        does not match or a prompt that is too long raises ValueError
+        where the other path asserts, and ``tokens.tolist()`` syncs
+        with the host if ``tokens`` is on the device."""
         cfg, w = self.cfg, self.weights
         Bp, S = tokens.shape
+        if self.sampling == "request" and self._packed_prefill_serves():
+            assert Bp <= self.B and S < cfg.max_seq_len
+            return self.prefill_packed(
+                tokens.tolist(), torch.as_tensor(slots).tolist(),
+                adapters=adapters)
         slots = torch.as_tensor(slots, dtype=torch.long,
                                 device=self.device)
         assert Bp == slots.numel() and Bp <= self.B
         assert S < cfg.max_seq_len
+        self._check_token_ids(tokens)
         plan = self._adapter_plan(adapters, slots, [S] * Bp)
         d = cfg.head_dim
         tokens = tokens.to(self.device)
@@ -919,7 +1119,9 @@ class LlamaDecodeEngine:
         self.cache_lens[slots] = S
         last = hidden.view(Bp, S, -1)[:, -1]
         logits = last @ w.lm_head.t()
-        if self.per_slot_temp:
+        if self.sampling == "request":
+            self._sample_slots(logits, slots)
+        elif self.per_slot_temp:
             scores = logits.float() / self.buf_temp[slots]
             u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
             self.buf_tokens[slots] = (
@@ -1029,7 +1231,9 @@ class LlamaDecodeEngine:
             cu_seqlens[1:] - cu_seqlens[:-1])
         last = hidden[cu_seqlens[1:].long() - 1]
         logits = last @ w.lm_head.t()
-        if self.per_slot_temp:
+        if self.sampling == "request":
+            self._sample_slots(logits, slots_long)
+        elif self.per_slot_temp:
             scores = logits.float() / self.buf_temp[slots_long]
             u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
             self.buf_tokens[slots_long] = (
@@ -1048,8 +1252,11 @@ class LlamaDecodeEngine:
         assert B == self.B, f"engine built for batch {self.B}, got {B}"
         assert S + max_new_tokens <= self.cfg.max_seq_len
         logits = self.prefill(tokens, adapters=adapters)
-        next_tokens = self._select_tokens(logits)
-        self.buf_tokens.copy_(next_tokens)
+        if self.sampling == "request":
+            next_tokens = self.buf_tokens.clone()  # sampled by prefill
+        else:
+            next_tokens = self._select_tokens(logits)
+            self.buf_tokens.copy_(next_tokens)
         generated = [next_tokens.clone()]
         if self.use_graph and self._graph is None:
             self.capture_graph()
@@ -1066,6 +1273,10 @@ class LlamaDecodeEngine:
                 f"speculative decoding conflicts with max_adapters="
                 f"{self.max_adapters}: the verify pass runs the base "
                 "weights only")
+        if self.sampling == "request":
+            raise ValueError(
+                'speculative decoding conflicts with sampling="request": '
+                "it is greedy only")
         if self.temperature > 0.0 or self.per_slot_temp:
             raise ValueError(
                 "speculative decoding is greedy only (temperature "
@@ -1305,6 +1516,16 @@ class LlamaServer:
       adapters.  ``max_adapters`` (default: their number) sizes the
       tables, ``lora_rank`` (8/16/32/64) is the table rank.  Not with
       ``speculative > 0``.  Adapters are fixed once ``load()`` ran.
+    - ``sampling``: "engine" (default) picks tokens with the engine-wide
+      ``temperature`` / ``top_k``; "request" gives every request its own
+      ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``seed`` and
+      ``logprobs`` fields on the fused ``ops.sample_tokens`` kernel, in
+      both schedulers and through the batcher.  The constructor's
+      ``temperature``, ``top_k``, ``top_p`` and ``min_p`` are then the
+      defaults of requests that omit them.  Prompt j of a request draws
+      with ``seed + j``; a request without a seed gets a random one.
+      A request's tokens depend on its prompt, seed and parameters
+      only.  Not with ``speculative > 0``.
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -1315,7 +1536,8 @@ class LlamaServer:
                  temperature: float = 0.0, top_k: int = 0,
                  prefill: str = "exact", speculative: int = 0,
                  adapters: dict = None, max_adapters: int = None,
-                 lora_rank: int = 16, **class_args):
+                 lora_rank: int = 16, sampling: str = "engine",
+                 top_p: float = 1.0, min_p: float = 0.0, **class_args):
         import queue as queue_mod
         import threading
 
@@ -1365,6 +1587,22 @@ class LlamaServer:
         self.lora_rank = int(lora_rank)
         self._lora_requests = {name: 0 for name in self.adapters}
         self._lora_lock = threading.Lock()
+        if sampling not in ("engine", "request"):
+            raise ValueError(f"unknown sampling mode {sampling!r} "
+                             "(expected 'engine' or 'request')")
+        self.sampling = sampling
+        self._sampling_defaults = None
+        self._sampling_counts = {"requests": 0, "sampled": 0, "greedy": 0}
+        if sampling == "request":
+            if self.temperature < 0:
+                raise ValueError(
+                    f"temperature={temperature} conflicts with "
+                    'sampling="request": per-slot temperatures are the '
+                    "request field there, the default must be >= 0")
+            # the constructor's values are the requests' defaults
+            self._sampling_defaults = SamplingParams(
+                temperature=temperature, top_k=top_k, top_p=top_p,
+                min_p=min_p).validate()
         self._check_speculative_config()
         self.replicas = max(int(replicas), 1)
         self.engines: typing.List[LlamaDecodeEngine] = []
@@ -1386,6 +1624,10 @@ class LlamaServer:
         k = self.speculative
         if k == 0:
             return
+        if self.sampling == "request":
+            raise ValueError(
+                f'speculative={k} conflicts with sampling="request": '
+                "speculative decoding is greedy only")
         if self.max_adapters > 0:
             raise ValueError(
                 f"speculative={k} conflicts with LoRA adapters "
@@ -1451,22 +1693,28 @@ class LlamaServer:
                 'kv_dtype="bf16" or prefill="exact"')
         if not torch.cuda.is_available():
             self.replicas = 1
+        # sampling="request": the engine-wide temperature / top_k stay
+        # off, the constructor's values are per-request defaults
+        by_request = self.sampling == "request"
+        engine_temp = 0.0 if by_request else self.temperature
+        engine_top_k = 0 if by_request else self.top_k
         first = LlamaDecodeEngine(cfg, self.batch_size, device=self.device,
                                   use_graph=self.use_graph,
                                   weight_dtype=self.weight_dtype,
                                   kv_dtype=self.kv_dtype,
-                                  temperature=self.temperature,
-                                  top_k=self.top_k,
+                                  temperature=engine_temp,
+                                  top_k=engine_top_k,
                                   max_adapters=self.max_adapters,
-                                  lora_rank=self.lora_rank)
+                                  lora_rank=self.lora_rank,
+                                  sampling=self.sampling)
         self.engines = [first]
         for _ in range(self.replicas - 1):
             replica = LlamaDecodeEngine(
                 cfg, self.batch_size, device=self.device,
                 use_graph=self.use_graph, weights=first.weights,
                 weight_dtype="bf16", kv_dtype=self.kv_dtype,
-                temperature=self.temperature, top_k=self.top_k,
-                lora=first.lora)
+                temperature=engine_temp, top_k=engine_top_k,
+                lora=first.lora, sampling=self.sampling)
             replica.weight_dtype = first.weight_dtype
             replica._fp8_packs = first._fp8_packs  # shared packs
             if first.weight_dtype == "fp8w" and replica.on_gpu:
@@ -1543,34 +1791,39 @@ class LlamaServer:
                 return
             prompts, max_new, future = item[:3]
             ids = item[3] if len(item) > 3 else None  # adapter slots
+            # SamplingParams per prompt (sampling="request")
+            params = item[4] if len(item) > 4 else None
             try:
                 if engine._serve_stream is not None:
                     with torch.cuda.stream(engine._serve_stream):
                         result = self._generate_on(engine, prompts,
-                                                   max_new, ids)
+                                                   max_new, ids, params)
                     engine._serve_stream.synchronize()
                 else:
                     result = self._generate_on(engine, prompts, max_new,
-                                               ids)
+                                               ids, params)
                 future.set_result(result)
             except Exception as exc:
                 if not future.done():
                     future.set_exception(exc)
 
     def _stream_generate(self, inputs, max_new, event, req_temp=None,
-                         adapter_id=-1):
+                         adapter_id=-1, params=None):
         """Token streaming (continuous scheduling only): yields one
-        json line per generated token as the slots produce them."""
+        json line per generated token as the slots produce them; with
+        ``"logprobs": true`` (sampling="request") a line carries the
+        token's "logprob" as well."""
         import concurrent.futures
         import json as _json
         import queue as queue_mod
 
         streams = []
-        for prompt in inputs:
+        for j, prompt in enumerate(inputs):
             future = concurrent.futures.Future()
             stream_q: "queue_mod.Queue" = queue_mod.Queue()
             self._tasks.put((prompt, max_new, future, stream_q,
-                             req_temp, adapter_id))
+                             req_temp, adapter_id,
+                             params[j] if params else None))
             streams.append(stream_q)
 
         def gen():
@@ -1586,9 +1839,10 @@ class LlamaServer:
                     if token is None:
                         active.remove(stream_q)
                         continue
-                    yield _json.dumps(
-                        {"index": indexes[id(stream_q)],
-                         "token": token}) + "\n"
+                    line = {"index": indexes[id(stream_q)], "token": token}
+                    if isinstance(token, tuple):  # (token, logprob)
+                        line["token"], line["logprob"] = token
+                    yield _json.dumps(line) + "\n"
 
         return gen()
 
@@ -1598,7 +1852,8 @@ class LlamaServer:
         admitted at token boundaries via ``prefill_slots`` — no
         generate-pass barrier (vLLM-style scheduling on the fixed-B
         hipGraph).  Each request is one queue item (prompt, max_new,
-        future[, stream queue[, temperature[, adapter slot]]])."""
+        future[, stream queue[, temperature[, adapter slot[,
+        SamplingParams]]]])."""
         import contextlib
         import queue as queue_mod
 
@@ -1608,6 +1863,16 @@ class LlamaServer:
                                device=engine.device)
         slots: list = [None] * B
         step = 0
+        # sampling="request": a logprob ring next to the token ring, and
+        # every result is a (tokens, logprobs) pair
+        by_request = engine.sampling == "request"
+        lp_ring = torch.empty(B, ring_len, dtype=torch.float32,
+                              device=engine.device) if by_request else None
+
+        def emit(state, token, logprob):
+            """One streamed token, with its logprob when asked for."""
+            state["stream"].put((token, float(logprob))
+                                if state["logprobs"] else token)
 
         def stream_ctx():
             return torch.cuda.stream(engine._serve_stream) \
@@ -1640,11 +1905,16 @@ class LlamaServer:
             if taken:
                 self.engine_calls += 1
                 prompts, admit_slots, admit_ids = [], [], []
+                admit_params = []
                 for item, slot in zip(taken, free):
                     prompt, max_new, future = item[:3]
                     stream_q = item[3] if len(item) > 3 else None
                     temp = item[4] if len(item) > 4 else None
                     admit_ids.append(item[5] if len(item) > 5 else -1)
+                    params = item[6] if len(item) > 6 else None
+                    if by_request and params is None:
+                        params = self._sampling_defaults
+                    admit_params.append(params)
                     if engine.per_slot_temp:
                         engine.buf_temp[slot] = max(
                             float(temp or 0.0), 1e-4)
@@ -1656,7 +1926,9 @@ class LlamaServer:
                     admit_slots.append(slot)
                     slots[slot] = {"future": future, "max_new": max_new,
                                    "start": step, "produced": 1,
-                                   "stream": stream_q}
+                                   "stream": stream_q,
+                                   "logprobs": bool(
+                                       by_request and params.logprobs)}
                 # prefill per EXACT prompt length: left-padding a
                 # mixed-length admission group would make a request's
                 # output depend on co-arriving traffic (pad tokens are
@@ -1668,6 +1940,12 @@ class LlamaServer:
                         (prompt, slot, aid))
                 lora_on = engine.lora is not None
                 try:
+                    if by_request:
+                        # the slots' parameters, before their prefill
+                        # samples the first token with them
+                        with stream_ctx():
+                            engine.set_sampling_slots(admit_slots,
+                                                      admit_params)
                     if self.prefill == "packed":
                         # the whole mixed-length group in ONE pass:
                         # packed rows carry no padding, so the result
@@ -1683,6 +1961,9 @@ class LlamaServer:
                                 engine.prefill_packed(prompts, admit_slots)
                             out_ring[slot_ids, step % ring_len] = \
                                 engine.buf_tokens[slot_ids]
+                            if by_request:
+                                lp_ring[slot_ids, step % ring_len] = \
+                                    engine.buf_logprob[slot_ids]
                     for length, group in by_len.items():
                         tokens = torch.tensor(
                             [g[0] for g in group], dtype=torch.int64)
@@ -1697,8 +1978,21 @@ class LlamaServer:
                                 engine.prefill_slots(tokens, slot_ids)
                             out_ring[slot_ids, step % ring_len] = \
                                 engine.buf_tokens[slot_ids]
+                            if by_request:
+                                lp_ring[slot_ids, step % ring_len] = \
+                                    engine.buf_logprob[slot_ids]
                 except Exception as exc:  # admission failed: fail the
-                    for slot in admit_slots:  # requests, free the slots
+                    if by_request:            # requests, free the slots
+                        # freed slots decode on: back to greedy, like
+                        # every other path that frees one
+                        try:
+                            with stream_ctx():
+                                engine.set_sampling_slots(
+                                    admit_slots, [None] * len(admit_slots))
+                        except Exception as reset_exc:
+                            logger.error("sampling reset failed",
+                                         error=str(reset_exc))
+                    for slot in admit_slots:
                         state = slots[slot]
                         if state is None:
                             continue
@@ -1719,18 +2013,27 @@ class LlamaServer:
                     if engine._serve_stream is not None:
                         engine._serve_stream.synchronize()
                     first = engine.buf_tokens.cpu()
+                    first_lp = engine.buf_logprob.cpu() if by_request \
+                        else None
                     for slot in admit_slots:
                         state = slots[slot]
                         token = int(first[slot])
                         if token != self.stop_token and \
                                 state["max_new"] > 1:
                             continue
+                        logprob = float(first_lp[slot]) if by_request \
+                            else None
                         if state["stream"]:
-                            state["stream"].put(token)
+                            emit(state, token, logprob)
                             state["stream"].put(None)
                             state["_first_sent"] = True
-                        state["future"].set_result([token])
+                        state["future"].set_result(
+                            ([token], [logprob]) if by_request
+                            else [token])
                         slots[slot] = None
+                        if by_request:
+                            with stream_ctx():
+                                engine.set_sampling_slots([slot], [None])
             active = [i for i in range(B) if slots[i] is not None]
             if not active:
                 continue
@@ -1744,20 +2047,26 @@ class LlamaServer:
                             not state.get("_first_sent"):
                         if engine._serve_stream is not None:
                             engine._serve_stream.synchronize()
-                        state["stream"].put(int(
-                            out_ring[i, state["start"] % ring_len]))
+                        col = state["start"] % ring_len
+                        emit(state, int(out_ring[i, col]),
+                             lp_ring[i, col] if by_request else None)
                         state["_first_sent"] = True
             with stream_ctx():
                 engine.decode_step()
                 step += 1
                 out_ring[:, step % ring_len].copy_(engine.buf_tokens)
+                if by_request:
+                    lp_ring[:, step % ring_len].copy_(engine.buf_logprob)
             host_tokens = None
             if streaming or stop is not None:
                 if engine._serve_stream is not None:
                     engine._serve_stream.synchronize()
                 host_tokens = engine.buf_tokens.cpu()
+                host_lp = engine.buf_logprob.cpu() \
+                    if by_request and streaming else None
                 for i in streaming:
-                    slots[i]["stream"].put(int(host_tokens[i]))
+                    emit(slots[i], int(host_tokens[i]),
+                         host_lp[i] if by_request else None)
             finished = []
             for i in active:
                 state = slots[i]
@@ -1776,8 +2085,11 @@ class LlamaServer:
                         [(state["start"] + j) % ring_len
                          for j in range(state["max_new"])],
                         dtype=torch.long)
-                    result = out_ring[i, cols.to(out_ring.device)]
-                    state["future"].set_result(result.cpu().tolist())
+                    cols = cols.to(out_ring.device)
+                    result = out_ring[i, cols].cpu().tolist()
+                    if by_request:
+                        result = (result, lp_ring[i, cols].cpu().tolist())
+                    state["future"].set_result(result)
                     if state["stream"]:
                         state["stream"].put(None)  # end-of-stream
                     slots[i] = None
@@ -1787,6 +2099,11 @@ class LlamaServer:
                     with stream_ctx():
                         engine.buf_adapter[torch.tensor(
                             finished, dtype=torch.long)] = -1
+                if by_request:
+                    # freed slots keep stepping too: greedy is cheapest
+                    with stream_ctx():
+                        engine.set_sampling_slots(
+                            finished, [None] * len(finished))
 
     def do_event(self, event):
         import concurrent.futures
@@ -1804,39 +2121,79 @@ class LlamaServer:
         max_new = int(body.get("max_tokens", self.max_new_tokens))
         req_temp = body.get("temperature")
         adapter_id = self._adapter_slot(body.get("adapter"))
+        # sampling="request": one SamplingParams per prompt, else None
+        params = self._request_sampling(body, len(inputs))
+        if params is not None:
+            req_temp = None  # "temperature" is a SamplingParams field
         if self.scheduling == "continuous" and body.get("stream"):
             event.body = self._stream_generate(inputs, max_new, event,
-                                               req_temp, adapter_id)
+                                               req_temp, adapter_id, params)
             return event
         if self.scheduling == "continuous":
             futures = []
-            for prompt in inputs:
+            for j, prompt in enumerate(inputs):
                 future = concurrent.futures.Future()
                 self._tasks.put((prompt, max_new, future, None,
-                                 req_temp, adapter_id))
+                                 req_temp, adapter_id,
+                                 params[j] if params else None))
                 futures.append(future)
             outputs = [f.result(timeout=600) for f in futures]
         elif self.batch_window_ms and len(inputs) < self.batch_size:
-            outputs = self._batched_submit(inputs, max_new, adapter_id)
+            outputs = self._batched_submit(inputs, max_new, adapter_id,
+                                           params)
         else:
             futures = []
             for chunk_start in range(0, len(inputs), self.batch_size):
                 chunk = inputs[chunk_start:chunk_start + self.batch_size]
                 future = concurrent.futures.Future()
-                self._tasks.put((chunk, max_new, future,
-                                 [adapter_id] * len(chunk)))
+                self._tasks.put((
+                    chunk, max_new, future, [adapter_id] * len(chunk),
+                    params[chunk_start:chunk_start + self.batch_size]
+                    if params else None))
                 futures.append(future)
             outputs = []
             for future in futures:
                 outputs.extend(future.result(timeout=600))
         event.body = {"id": event.id, "model_name": self.name,
                       "outputs": outputs}
+        if params is not None:
+            # rows are (tokens, logprobs) pairs in this mode
+            event.body["outputs"] = [row[0] for row in outputs]
+            if body.get("logprobs"):
+                event.body["logprobs"] = [row[1] for row in outputs]
         if "retrieval" in body:  # RAG upstream step metadata
             event.body["retrieval"] = body["retrieval"]
         if self._model_logger:
             self._model_logger.push(start, {"inputs": [len(inputs)]},
                                     event.body)
         return event
+
+    def _request_sampling(self, body: dict, n_prompts: int):
+        """The request's sampling fields as one SamplingParams per
+        prompt (sampling="request"; None otherwise, and then no field
+        is looked at).  Absent fields take the server's defaults, prompt
+        j draws with seed + j, an absent seed is drawn at random.  A
+        field out of range is a ValueError naming it, which fails this
+        request alone."""
+        if self.sampling != "request":
+            return None
+        import dataclasses
+        import random
+
+        base = self._sampling_defaults
+        fields = {name: body[name] for name in
+                  ("temperature", "top_k", "top_p", "min_p", "seed",
+                   "logprobs") if body.get(name) is not None}
+        first = dataclasses.replace(base, **fields).validate()
+        if "seed" not in fields:
+            first.seed = random.SystemRandom().getrandbits(63)
+        with self._lora_lock:
+            self._sampling_counts["requests"] += 1
+            self._sampling_counts[
+                "sampled" if first.temperature > 0 else "greedy"] += 1
+        return [dataclasses.replace(first,
+                                    seed=(first.seed + j) % (1 << 63))
+                for j in range(n_prompts)]
 
     def _adapter_slot(self, name) -> int:
         """Table slot of a request's "adapter" field; absent or null
@@ -1853,7 +2210,7 @@ class LlamaServer:
         return self.adapter_slots[name]
 
     def _batched_submit(self, inputs: list, max_new: int,
-                        adapter_id: int = -1) -> list:
+                        adapter_id: int = -1, params: list = None) -> list:
         """Queue small requests; the batcher gathers up to batch_size
         prompts within batch_window_ms and submits ONE engine task."""
         import concurrent.futures
@@ -1866,10 +2223,10 @@ class LlamaServer:
                     target=self._batch_loop, daemon=True,
                     name=f"llama-batcher-{self.name}")
                 self._batcher.start()
-            for prompt in inputs:
+            for j, prompt in enumerate(inputs):
                 future = concurrent.futures.Future()
-                self._pending.append((prompt, max_new, future,
-                                      adapter_id))
+                self._pending.append((prompt, max_new, future, adapter_id,
+                                      params[j] if params else None))
                 futures.append(future)
             self._pending_cv.notify()
         return [f.result(timeout=600) for f in futures]
@@ -1896,28 +2253,46 @@ class LlamaServer:
             task_future = concurrent.futures.Future()
             # one engine pass may mix adapters: one id per prompt
             ids = [b[3] if len(b) > 3 else -1 for b in batch]
-            self._tasks.put((prompts, max_new, task_future, ids))
+            # ... and parameter sets: one SamplingParams per prompt
+            params = [b[4] if len(b) > 4 else None for b in batch]
+            self._tasks.put((prompts, max_new, task_future, ids, params))
             try:
                 results = task_future.result(timeout=600)
                 for entry, result in zip(batch, results):
-                    entry[2].set_result(result[:entry[1]])
+                    if isinstance(result, tuple):  # (tokens, logprobs)
+                        result = tuple(part[:entry[1]] for part in result)
+                    else:
+                        result = result[:entry[1]]
+                    entry[2].set_result(result)
             except Exception as exc:
                 for entry in batch:
                     if not entry[2].done():
                         entry[2].set_exception(exc)
 
     def _generate_on(self, engine: LlamaDecodeEngine, prompts: list,
-                     max_new: int, adapters: list = None) -> list:
+                     max_new: int, adapters: list = None,
+                     params: list = None) -> list:
         """Batch generation with per-LENGTH prefill groups: padding a
         mixed-length batch would let pad tokens be attended, making a
         prompt's output depend on its co-batch (see the continuous
-        scheduler property test)."""
+        scheduler property test).  On a sampling="request" engine
+        ``params`` holds one SamplingParams per prompt (None = the
+        server's defaults) and every row of the result is a
+        (tokens, logprobs) pair."""
         self.engine_calls += 1
         n = len(prompts)
         by_len: dict = {}
         for i, prompt in enumerate(prompts):
             by_len.setdefault(len(prompt), []).append(i)
         engine.reset()
+        by_request = engine.sampling == "request"
+        if by_request:
+            # rows beyond n decode greedily: they are never read
+            row_params = [self._sampling_defaults] * n if params is None \
+                else [self._sampling_defaults if item is None else item
+                      for item in params]
+            engine.set_sampling_slots(
+                range(engine.B), row_params + [None] * (engine.B - n))
         lora_on = engine.lora is not None
         if lora_on:
             engine.buf_adapter.fill_(-1)  # rows beyond n run the base
@@ -1936,9 +2311,12 @@ class LlamaServer:
             if engine.use_graph and engine._graph is None:
                 engine.capture_graph()
             generated = [engine.buf_tokens.clone()]
+            logprobs = [engine.buf_logprob.clone()] if by_request else None
             for _ in range(max_new - 1):
                 engine.decode_step()
                 generated.append(engine.buf_tokens.clone())
+                if by_request:
+                    logprobs.append(engine.buf_logprob.clone())
             out = torch.stack(generated, dim=1)
         rows = out[:n].cpu().tolist()
         if self.stop_token is not None:
@@ -1947,7 +2325,10 @@ class LlamaServer:
                 if self.stop_token in row:
                     row = row[:row.index(self.stop_token) + 1]
                 trimmed.append(row)
-            return trimmed
+            rows = trimmed
+        if by_request:
+            lp_rows = torch.stack(logprobs, dim=1)[:n].cpu().tolist()
+            return [(row, lp[:len(row)]) for row, lp in zip(rows, lp_rows)]
         return rows
 
     def _speculate_on(self, engine: LlamaDecodeEngine, prompts: list,
@@ -1983,6 +2364,13 @@ class LlamaServer:
         return request.get("inputs"), None
 
     def stats(self):
+        if self.sampling == "request":
+            with self._lora_lock:
+                out = {"sampling": dict(self._sampling_counts)}
+                if self.adapters:
+                    out["lora"] = {"adapters": list(self.adapters),
+                                   "requests": dict(self._lora_requests)}
+            return out
         if self.adapters:
             with self._lora_lock:
                 counts = dict(self._lora_requests)

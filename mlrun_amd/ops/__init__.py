@@ -739,6 +739,227 @@ def lora_expand(y: torch.Tensor, t: torch.Tensor, Bm: torch.Tensor,
     return y
 
 
+# ---------------------------------------------------------------- sampler
+
+SAMPLE_MAX_ROWS = 64           # logits rows per launch
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)   # round multipliers
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)   # key increments
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) on numpy arrays: ``counter``
+    is four and ``key`` two broadcastable arrays of 32-bit words; returns
+    the output blocks as uint32 [..., 4]."""
+    import numpy as np
+
+    u64 = np.uint64
+    mask, shift = u64(0xFFFFFFFF), u64(32)
+    c = [np.asarray(word).astype(u64) for word in counter]
+    k = [np.asarray(word).astype(u64) for word in key]
+    for _ in range(10):
+        p0 = u64(_PHILOX_M[0]) * c[0]
+        p1 = u64(_PHILOX_M[1]) * c[2]
+        c = [(p1 >> shift) ^ c[1] ^ k[0], p1 & mask,
+             (p0 >> shift) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + u64(_PHILOX_W[0])) & mask,
+             (k[1] + u64(_PHILOX_W[1])) & mask]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def sample_tokens_reference(logits, pos, temperature, top_k, top_p, min_p,
+                            seed) -> dict:
+    """The sampler's semantics, vectorised over rows in numpy; this is
+    what ``sample_tokens`` computes for CPU tensors and what the kernel
+    is tested against.  Takes the arguments of ``sample_tokens`` (any
+    device) and returns numpy arrays: ``tokens`` int64, ``logprob`` f32
+    and ``kept`` int32 per row, plus the intermediates a test needs to
+    judge near-ties: ``s`` and ``u`` [B, V] f32, ``keep`` [B, V] bool,
+    ``q`` [B, V] and ``Q``, ``need`` [B] uint64 and, for the top_p cut,
+    ``tail_cut`` / ``tail_above`` [B] uint64 (the tail mass at the
+    threshold value and at the next larger distinct value).  Rows with
+    ``pos < 0`` are computed like the others; the caller skips them.
+
+    Per row, z_i = float(logits[i]):
+    - temperature == 0: argmax z, lowest index on ties, kept = 1.  The
+      same holds for any temperature at which zmax / T (f32) is not the
+      finite quotient of a positive T: negative, NaN, or so small that
+      the division overflows.  No score can then be NaN or +inf.
+    - otherwise s_i = z_i / T (f32), m = max s, e_i = expf(s_i - m),
+      q_i = floor(e_i * 2^32 + 0.5) (u64, exact in f64), Q = sum q_i.
+      A token is kept if it passes every active filter, each a threshold
+      on the logit value (equal logits stay together):
+      top_k (0 < k < V): z_i >= the k-th largest value;
+      top_p (p < 1): z_i >= v*, the largest value whose tail mass
+      sum_{z_j >= v*} q_j reaches need = ceil(f64(p) * f64(Q));
+      min_p (> 0): f64(q_i) >= f64(min_p) * 2^32.
+      need is at least 1 (top_p <= 0 keeps the maximum's tie group), and
+      a row whose filters keep nothing (min_p > 1) falls back to the
+      argmax with kept = 1: the token is always a valid index.
+      The token is the argmax over kept i of s_i + g_i (lowest index on
+      ties), g_i = -logf(-logf(u_i)), u_i = ((r_i >> 8) + 0.5) * 2^-24
+      in f32 and at most 1 - 2^-24, r_i = word i & 3 of the Philox4x32-10
+      block with counter (i >> 2, pos, 0, 0) and key (seed & 0xffffffff,
+      seed >> 32).
+    - logprob = (z_tok - zmax) - logf(sum expf(z_i - zmax)): the model's
+      own distribution at T = 1, unfiltered."""
+    import numpy as np
+
+    f32, f64, u64 = np.float32, np.float64, np.uint64
+    z = logits.detach().float().cpu().numpy()
+    B, V = z.shape
+    rows = np.arange(B)
+    pos = pos.detach().cpu().numpy().astype(np.int64)
+    T = temperature.detach().cpu().numpy().astype(f32)
+    k = top_k.detach().cpu().numpy().astype(np.int64)
+    p = top_p.detach().cpu().numpy().astype(f32)
+    mp = min_p.detach().cpu().numpy().astype(f32)
+    sd = seed.detach().cpu().numpy().astype(np.int64).astype(u64)
+    zmax = z.max(axis=1)
+    with np.errstate(all="ignore"):
+        sampled = (T > 0) & np.isfinite(
+            (zmax / np.where(T > 0, T, f32(1))).astype(f32))
+    s = (z / np.where(sampled, T, f32(1))[:, None]).astype(f32)
+    m = s.max(axis=1)
+    e = np.exp((s - m[:, None]).astype(f32)).astype(f32)
+    q = np.floor(e.astype(f64) * 4294967296.0 + 0.5).astype(u64)
+    Q = q.sum(axis=1, dtype=u64)
+    order = np.argsort(-z, axis=1, kind="stable")
+    z_sorted = np.take_along_axis(z, order, axis=1)
+    # top_k: the k-th largest value
+    k_on = sampled & (k > 0) & (k < V)
+    kth = z_sorted[rows, np.clip(k - 1, 0, V - 1)]
+    keep = ~k_on[:, None] | (z >= kth[:, None])
+    # top_p: first sorted index whose running mass reaches need; its
+    # value is v* (its whole tie group ends at or after that index)
+    p_on = sampled & (p < 1)
+    need = np.maximum(np.ceil(np.where(p > 0, p, f32(0)).astype(f64)
+                              * Q.astype(f64)), 1.0).astype(u64)
+    cum = np.cumsum(np.take_along_axis(q, order, axis=1), axis=1, dtype=u64)
+    cut = (cum >= need[:, None]).argmax(axis=1)
+    v_star = z_sorted[rows, cut]
+    keep &= ~p_on[:, None] | (z >= v_star[:, None])
+    ge = z_sorted >= v_star[:, None]        # sorted: a prefix of each row
+    gt = z_sorted > v_star[:, None]
+    tail_cut = cum[rows, ge.sum(axis=1) - 1]
+    n_gt = gt.sum(axis=1)
+    tail_above = np.where(n_gt > 0, cum[rows, np.maximum(n_gt, 1) - 1],
+                          u64(0)).astype(u64)
+    # min_p
+    mp_on = sampled & (mp > 0)
+    keep &= ~mp_on[:, None] | (q.astype(f64) >=
+                               mp.astype(f64)[:, None] * 4294967296.0)
+    # counter-based noise: block c serves tokens 4c .. 4c + 3
+    blocks = philox4x32(
+        (np.arange(V // 4, dtype=u64)[None, :],
+         (pos & 0xFFFFFFFF).astype(u64)[:, None], 0, 0),
+        ((sd & u64(0xFFFFFFFF))[:, None], (sd >> u64(32))[:, None]))
+    r = blocks.reshape(B, V)
+    u = ((r >> np.uint32(8)).astype(f32) + f32(0.5)) * f32(2.0 ** -24)
+    u = np.minimum(u, f32(1.0 - 2.0 ** -24)).astype(f32)
+    g = (-np.log(-np.log(u))).astype(f32)
+    drawn = sampled & keep.any(axis=1)      # nothing kept: the argmax
+    score = np.where(keep, (s + g).astype(f32), f32(-np.inf))
+    tokens = np.where(drawn, score.argmax(axis=1), z.argmax(axis=1))
+    kept = np.where(drawn, keep.sum(axis=1), 1).astype(np.int32)
+    lsum = np.exp((z - zmax[:, None]).astype(f32)).sum(axis=1, dtype=f32)
+    logprob = ((z[rows, tokens] - zmax).astype(f32)
+               - np.log(lsum).astype(f32)).astype(f32)
+    return {"tokens": tokens.astype(np.int64), "logprob": logprob,
+            "kept": kept, "s": s, "u": u, "keep": keep, "q": q, "Q": Q,
+            "need": need, "tail_cut": tail_cut, "tail_above": tail_above}
+
+
+def _check_sample(logits, per_row, out_tokens, out_logprob, out_kept):
+    """Argument checks of sample_tokens; ValueError before any launch."""
+    checks = [("logits", logits, torch.bfloat16)]
+    checks += [(name, tensor, dtype) for name, (tensor, dtype)
+               in per_row.items()]
+    checks.append(("out_tokens", out_tokens, torch.int64))
+    if out_logprob is not None:
+        checks.append(("out_logprob", out_logprob, torch.float32))
+    if out_kept is not None:
+        checks.append(("out_kept", out_kept, torch.int32))
+    for name, tensor, dtype in checks:
+        if not isinstance(tensor, torch.Tensor):
+            raise ValueError(f"sample_tokens: {name} must be a tensor")
+        if tensor.dtype != dtype:
+            raise ValueError(f"sample_tokens: {name} must be {dtype}, got "
+                             f"{tensor.dtype}")
+        if not tensor.is_contiguous():
+            raise ValueError(f"sample_tokens: {name} must be contiguous")
+        if tensor.device != logits.device:
+            raise ValueError(f"sample_tokens: {name} is on {tensor.device}, "
+                             f"logits on {logits.device}")
+    if logits.dim() != 2:
+        raise ValueError("sample_tokens: logits must be [B, V], got "
+                         f"{tuple(logits.shape)}")
+    B, V = logits.shape
+    if B > SAMPLE_MAX_ROWS:
+        raise ValueError(f"sample_tokens: B must be <= {SAMPLE_MAX_ROWS}, "
+                         f"got {B}")
+    if V == 0 or V % 8 or V >= 1 << 24:
+        raise ValueError("sample_tokens: V must be a positive multiple of "
+                         f"8 below 2^24, got {V}")
+    for name, tensor, _ in checks[1:]:
+        if tensor.dim() != 1 or tensor.numel() != B:
+            raise ValueError(f"sample_tokens: {name} must be [{B}], got "
+                             f"{tuple(tensor.shape)}")
+    if logits.is_cuda and logits.data_ptr() % 16:
+        raise ValueError("sample_tokens: logits must be 16-byte aligned "
+                         "(a view at an offset that is no multiple of 8 "
+                         "elements is not)")
+
+
+def sample_tokens(logits: torch.Tensor, pos: torch.Tensor,
+                  temperature: torch.Tensor, top_k: torch.Tensor,
+                  top_p: torch.Tensor, min_p: torch.Tensor,
+                  seed: torch.Tensor, out_tokens: torch.Tensor,
+                  out_logprob: torch.Tensor = None,
+                  out_kept: torch.Tensor = None) -> torch.Tensor:
+    """Fused per-row sampler: temperature, top_k, top_p, min_p and a
+    seeded Gumbel-max draw in one launch, with the chosen token's
+    logprob.  Every parameter is a tensor on the logits' device, read
+    at run time: no allocation, no sync, hipGraph-capture safe.
+
+    logits [B, V] bf16 (B <= 64, V % 8 == 0); pos [B] int32 (the
+    position of the token being generated: the noise counter);
+    temperature / top_p / min_p [B] f32; top_k [B] int32; seed [B]
+    int64; out_tokens [B] int64; out_logprob [B] f32 and out_kept [B]
+    int32 optional.  temperature 0 = greedy, top_k 0 / top_p 1 /
+    min_p 0 = filter off.  Rows with pos < 0 are skipped and leave all
+    outputs untouched.  A row's result depends only on its own logits
+    and parameters, never on B or on the other rows, and is bitwise
+    reproducible.  The exact semantics: ``sample_tokens_reference``.
+    Logits must be finite.  Parameters outside their ranges (temperature
+    < 0, NaN or too small to divide by, top_p <= 0, min_p > 1) degrade
+    to the argmax as the reference states, never to an invalid token.
+    Bad shapes, dtypes or layouts, logits not 16-byte aligned on the
+    GPU included, raise ValueError before any launch."""
+    _check_sample(
+        logits,
+        {"pos": (pos, torch.int32), "temperature": (temperature,
+                                                    torch.float32),
+         "top_k": (top_k, torch.int32), "top_p": (top_p, torch.float32),
+         "min_p": (min_p, torch.float32), "seed": (seed, torch.int64)},
+        out_tokens, out_logprob, out_kept)
+    if logits.is_cuda:
+        _require_hip().sample_tokens(logits, pos, temperature, top_k, top_p,
+                                     min_p, seed, out_tokens, out_logprob,
+                                     out_kept)
+        return out_tokens
+    if logits.shape[0] == 0:
+        return out_tokens
+    ref = sample_tokens_reference(logits, pos, temperature, top_k, top_p,
+                                  min_p, seed)
+    live = pos >= 0
+    out_tokens[live] = torch.from_numpy(ref["tokens"])[live]
+    if out_logprob is not None:
+        out_logprob[live] = torch.from_numpy(ref["logprob"])[live]
+    if out_kept is not None:
+        out_kept[live] = torch.from_numpy(ref["kept"])[live]
+    return out_tokens
+
+
 def kv_append(k_cache, v_cache, k_new, v_new, positions):
     """Scatter the new token K/V into the cache at positions[b]."""
     if k_cache.is_cuda:

@@ -539,6 +539,59 @@ void lora_expand(torch::Tensor y, torch::Tensor t, torch::Tensor Bm,
                      (int)t.size(1), (int)y.size(1), stream());
 }
 
+// fused per-request sampler: one workgroup per logits row
+void sample_tokens(torch::Tensor logits, torch::Tensor pos,
+                   torch::Tensor temperature, torch::Tensor top_k,
+                   torch::Tensor top_p, torch::Tensor min_p,
+                   torch::Tensor seed, torch::Tensor out_tokens,
+                   c10::optional<torch::Tensor> out_logprob,
+                   c10::optional<torch::Tensor> out_kept) {
+  CHECK_DEV(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
+  CHECK_DEV(pos); CHECK_CONTIG(pos); CHECK_I32(pos);
+  CHECK_DEV(temperature); CHECK_CONTIG(temperature); CHECK_F32(temperature);
+  CHECK_DEV(top_k); CHECK_CONTIG(top_k); CHECK_I32(top_k);
+  CHECK_DEV(top_p); CHECK_CONTIG(top_p); CHECK_F32(top_p);
+  CHECK_DEV(min_p); CHECK_CONTIG(min_p); CHECK_F32(min_p);
+  CHECK_DEV(seed); CHECK_CONTIG(seed);
+  CHECK_DEV(out_tokens); CHECK_CONTIG(out_tokens);
+  TORCH_CHECK(seed.scalar_type() == torch::kInt64 &&
+              out_tokens.scalar_type() == torch::kInt64,
+              "sample_tokens: seed and out_tokens must be int64");
+  TORCH_CHECK(logits.dim() == 2, "sample_tokens: logits must be [B, V]");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B <= 64, "sample_tokens: at most 64 rows, got ", B);
+  TORCH_CHECK(V % 8 == 0 && V < (1LL << 24),
+              "sample_tokens: V must be a multiple of 8 below 2^24, got ", V);
+  TORCH_CHECK(pos.numel() == B && temperature.numel() == B &&
+              top_k.numel() == B && top_p.numel() == B &&
+              min_p.numel() == B && seed.numel() == B &&
+              out_tokens.numel() == B,
+              "sample_tokens: every per-row tensor must hold B entries");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0,
+              "sample_tokens: logits must be 16-byte aligned");
+  void* logprob_ptr = nullptr;
+  void* kept_ptr = nullptr;
+  if (out_logprob.has_value()) {
+    CHECK_DEV(*out_logprob); CHECK_CONTIG(*out_logprob);
+    CHECK_F32(*out_logprob);
+    TORCH_CHECK(out_logprob->numel() == B,
+                "sample_tokens: out_logprob must hold B entries");
+    logprob_ptr = out_logprob->data_ptr();
+  }
+  if (out_kept.has_value()) {
+    CHECK_DEV(*out_kept); CHECK_CONTIG(*out_kept); CHECK_I32(*out_kept);
+    TORCH_CHECK(out_kept->numel() == B,
+                "sample_tokens: out_kept must hold B entries");
+    kept_ptr = out_kept->data_ptr();
+  }
+  if (B == 0) return;
+  launch_sample_tokens(logits.data_ptr(), pos.data_ptr(),
+                       temperature.data_ptr(), top_k.data_ptr(),
+                       top_p.data_ptr(), min_p.data_ptr(), seed.data_ptr(),
+                       out_tokens.data_ptr(), logprob_ptr, kept_ptr, (int)B,
+                       (int)V, stream());
+}
+
 void softmax(torch::Tensor out, torch::Tensor in) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(in); CHECK_CONTIG(in); CHECK_BF16(in);
@@ -704,6 +757,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_expand", &lora_expand, py::arg("y"), py::arg("t"),
         py::arg("bm"), py::arg("idx"),
         "multi-LoRA expand: y[b] += Bm[idx[b]] @ t[b], in place (bf16)");
+  m.def("sample_tokens", &sample_tokens, py::arg("logits"), py::arg("pos"),
+        py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("min_p"), py::arg("seed"), py::arg("out_tokens"),
+        py::arg("out_logprob") = py::none(),
+        py::arg("out_kept") = py::none(),
+        "fused seeded sampler: temperature, top_k, top_p, min_p, logprob");
   m.def("softmax", &softmax, "row softmax (bf16)");
   m.def("tree_ensemble", &tree_ensemble, "GBDT ensemble inference (f32)");
   m.def("window_ingest", &window_ingest,

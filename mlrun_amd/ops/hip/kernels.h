@@ -110,6 +110,13 @@ void launch_lora_expand(void* y, const void* t, const void* Bm,
                         const void* idx, int B, int NA, int R, int N,
                         void* stream);
 
+void launch_sample_tokens(const void* logits, const void* pos,
+                          const void* temperature, const void* top_k,
+                          const void* top_p, const void* min_p,
+                          const void* seed, void* out_tokens,
+                          void* out_logprob, void* out_kept, int B, int V,
+                          void* stream);
+
 void launch_softmax(void* out, const void* in, int rows, int cols,
                     void* stream);
 

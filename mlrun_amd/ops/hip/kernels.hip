@@ -2596,6 +2596,362 @@ void launch_lora_expand(void* y, const void* t, const void* Bm,
 }
 
 // ---------------------------------------------------------------------
+// Fused per-request sampler.  One workgroup per logits row [V] bf16;
+// every parameter of the row is read on the device, so a captured graph
+// follows whatever the host wrote last.  Semantics (shared with the CPU
+// reference in ops/__init__.py), z_i = float(logits[i]):
+//   T == 0: argmax z, lowest index on ties (filters ignored).  So is
+//           any T at which m = zmax / T is not a finite positive-T
+//           quotient (T < 0, NaN, or so small that the division
+//           overflows): no score can then be NaN or +inf.
+//   else  : s_i = z_i / T, m = max s, e_i = expf(s_i - m),
+//           q_i = floor(e_i * 2^32 + 0.5) as u64 (exact in double),
+//           Q = sum q_i.  A token is kept if its logit passes the top_k
+//           threshold (k-th largest value), the top_p threshold (largest
+//           value whose tail mass reaches ceil(p * Q)) and the min_p
+//           bound (q_i >= min_p * 2^32).  need is at least 1, and a row
+//           whose filters keep nothing (min_p > 1) falls back to the
+//           argmax with kept = 1, so the token is always below V.
+//           The draw is the argmax over the
+//           kept tokens of s_i + g_i, g_i Gumbel noise from Philox4x32-10
+//           keyed by the row's seed with counter (i >> 2, pos, 0, 0).
+// bf16 has 65536 values, so an order-preserving 16-bit key and a
+// two-level 256-bin histogram in LDS (integer counts for top_k, u64
+// masses for top_p) give both thresholds exactly, without a sort and in
+// any summation order.  The row (256 KB for llama-3) is re-read through
+// the caches in each pass.  Histograms are kept in SAMPLE_COPIES lane-striped
+// copies: randn-like logits put a third of a row into one bin, and 64
+// lanes adding to one LDS word serialise.
+// A row whose pos is negative is skipped before any barrier.
+// ---------------------------------------------------------------------
+#define SAMPLE_THREADS 1024
+#define SAMPLE_WAVES (SAMPLE_THREADS / 64)
+#define SAMPLE_COPIES 16
+
+// order-preserving 16-bit key of a bf16 bit pattern (-0 counts as +0)
+DEV unsigned int sample_key(unsigned short raw) {
+  unsigned int b = raw;
+  if (b == 0x8000u) b = 0u;
+  return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
+}
+
+DEV float sample_key_value(unsigned int key) {
+  const unsigned int b = (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu);
+  return bf2f((unsigned short)b);
+}
+
+DEV unsigned int sample_f32_ordered(float f) {
+  union { float f; uint32_t i; } v;
+  v.f = f;
+  return (v.i & 0x80000000u) ? ~v.i : (v.i | 0x80000000u);
+}
+
+// (key, index) packed so that a u64 max picks the largest key and, among
+// equal keys, the lowest index
+DEV unsigned long long sample_pack(unsigned int key, unsigned int index) {
+  return ((unsigned long long)key << 32) | (0xFFFFFFFFu - index);
+}
+
+DEV unsigned long long sample_mass(float e) {
+  return (unsigned long long)floor((double)e * 4294967296.0 + 0.5);
+}
+
+DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                       uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Gumbel noise of one random word: u = ((r >> 8) + 0.5) * 2^-24 in f32
+// (round to nearest even), kept below 1 so that g stays finite
+DEV float sample_gumbel(uint32_t r) {
+  float u = ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-08f;
+  u = fminf(u, 0.99999994f);
+  return -logf(-logf(u));
+}
+
+DEV unsigned long long sample_block_max(unsigned long long v,
+                                        unsigned long long* red, int tid) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, 64);
+    v = o > v ? o : v;
+  }
+  __syncthreads();  // red may still be read from an earlier reduction
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  unsigned long long r = red[0];
+#pragma unroll
+  for (int w = 1; w < SAMPLE_WAVES; ++w) r = red[w] > r ? red[w] : r;
+  return r;
+}
+
+DEV unsigned long long sample_block_sum(unsigned long long v,
+                                        unsigned long long* red, int tid) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  unsigned long long r = 0;
+#pragma unroll
+  for (int w = 0; w < SAMPLE_WAVES; ++w) r += red[w];
+  return r;
+}
+
+// fixed-order f32 sum: lane tree, then the wave partials in wave order
+DEV float sample_block_sumf(float v, float* red, int tid) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  float r = 0.f;
+#pragma unroll
+  for (int w = 0; w < SAMPLE_WAVES; ++w) r += red[w];
+  return r;
+}
+
+// hist holds 256 bins in SAMPLE_COPIES copies (bin * COPIES + copy).
+// Finds the highest bin at which the total of that bin and all bins
+// above it reaches `want` (>= 1); leaves the bin in sel[0] and the
+// total strictly above it in *above.  Called by the whole workgroup.
+template <typename T>
+DEV void sample_select(T* hist, T want, unsigned int* sel, T* above,
+                       int tid) {
+  __syncthreads();  // all adds to hist have landed
+  T total = 0;
+  if (tid < 256) {
+#pragma unroll
+    for (int c = 0; c < SAMPLE_COPIES; ++c)
+      total += hist[tid * SAMPLE_COPIES + c];
+    hist[tid * SAMPLE_COPIES] = total;  // own bin only
+  }
+  __syncthreads();
+  if (tid < 256) {
+    T over = 0;
+    for (int j = tid + 1; j < 256; ++j) over += hist[j * SAMPLE_COPIES];
+    if (over < want && over + total >= want) {
+      sel[0] = (unsigned int)tid;
+      *above = over;
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_tokens_kernel(
+    const unsigned short* __restrict__ logits, const int* __restrict__ pos,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, const float* __restrict__ min_p,
+    const long long* __restrict__ seed, long long* __restrict__ out_tokens,
+    float* __restrict__ out_logprob, int* __restrict__ out_kept, int V) {
+  __shared__ unsigned long long mass[256 * SAMPLE_COPIES];
+  __shared__ unsigned int cnt[256 * SAMPLE_COPIES];
+  __shared__ unsigned long long red64[SAMPLE_WAVES];
+  __shared__ float redf[SAMPLE_WAVES];
+  __shared__ unsigned int sel_k[1], sel_p[1];
+  __shared__ unsigned int above_k;
+  __shared__ unsigned long long above_p;
+
+  const int b = blockIdx.x;
+  const int position = pos[b];
+  if (position < 0) return;  // block-uniform, before any barrier
+  const int tid = threadIdx.x;
+  const int copy = tid & (SAMPLE_COPIES - 1);
+  const unsigned short* row = logits + (size_t)b * V;
+  const float T = temperature[b];
+  const int k = top_k[b];
+  const float p = top_p[b];
+  const float mp = min_p[b];
+  // pass 1 counts for top_k before the row is known to be sampled
+  const bool k_count = T > 0.f && k > 0 && k < V;
+  const double mp_bound = (double)mp * 4294967296.0;
+
+  for (int i = tid; i < 256 * SAMPLE_COPIES; i += SAMPLE_THREADS) {
+    cnt[i] = 0u;
+    mass[i] = 0ull;
+  }
+  if (tid == 0) {
+    sel_k[0] = 0u; sel_p[0] = 0u; above_k = 0u; above_p = 0ull;
+  }
+  __syncthreads();
+
+  // pass 1: the row maximum (lowest index on ties) and, for top_k, the
+  // counts by the high byte of the key
+  unsigned long long best = 0ull;
+  for (int v = tid * 8; v < V; v += SAMPLE_THREADS * 8) {
+    const short8v x = *reinterpret_cast<const short8v*>(row + v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const unsigned int key = sample_key((unsigned short)x[j]);
+      const unsigned long long packed = sample_pack(key, (unsigned)(v + j));
+      best = packed > best ? packed : best;
+      if (k_count) atomicAdd(&cnt[(key >> 8) * SAMPLE_COPIES + copy], 1u);
+    }
+  }
+  best = sample_block_max(best, red64, tid);
+  const unsigned int max_key = (unsigned int)(best >> 32);
+  const unsigned int max_index = 0xFFFFFFFFu - (unsigned int)best;
+  const float zmax = sample_key_value(max_key);
+  // greedy unless zmax / T is finite at T > 0: then every s_i <= m is
+  // finite or -inf, and no mass or score below can be NaN
+  const bool sampled = T > 0.f && isfinite(zmax / T);
+  const float m = sampled ? zmax / T : 0.f;
+  const bool k_on = sampled && k_count;
+  const bool p_on = sampled && p < 1.f;
+  const bool mp_on = sampled && mp > 0.f;
+
+  // pass 2: the T = 1 softmax denominator for the logprob and, for
+  // top_p, the fixed-point masses by the high byte of the key
+  float lsum = 0.f;
+  unsigned long long q_sum = 0ull;
+  for (int v = tid * 8; v < V; v += SAMPLE_THREADS * 8) {
+    const short8v x = *reinterpret_cast<const short8v*>(row + v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float z = bf2f((unsigned short)x[j]);
+      lsum += expf(z - zmax);
+      if (p_on) {
+        const unsigned int key = sample_key((unsigned short)x[j]);
+        const unsigned long long q = sample_mass(expf(z / T - m));
+        q_sum += q;
+        atomicAdd(&mass[(key >> 8) * SAMPLE_COPIES + copy], q);
+      }
+    }
+  }
+  lsum = sample_block_sumf(lsum, redf, tid);
+
+  unsigned int threshold = 0u;  // keep keys >= threshold
+  if (k_on || p_on) {
+    unsigned long long need = 0ull;
+    if (p_on) {
+      const unsigned long long Q = sample_block_sum(q_sum, red64, tid);
+      if (p > 0.f) need = (unsigned long long)ceil((double)p * (double)Q);
+      need = need > 0ull ? need : 1ull;  // p <= 0 keeps the maximum
+    }
+    if (k_on) sample_select(cnt, (unsigned int)k, sel_k, &above_k, tid);
+    if (p_on) sample_select(mass, need, sel_p, &above_p, tid);
+    const unsigned int bin_k = sel_k[0], bin_p = sel_p[0];
+    const unsigned int want_k = (unsigned int)k - above_k;
+    const unsigned long long want_p = need - above_p;
+    __syncthreads();  // everyone holds the level-1 result
+    for (int i = tid; i < 256 * SAMPLE_COPIES; i += SAMPLE_THREADS) {
+      cnt[i] = 0u;
+      mass[i] = 0ull;
+    }
+    __syncthreads();
+    // pass 3: the same two histograms by the low byte, inside the bins
+    // that hold the thresholds
+    for (int v = tid * 8; v < V; v += SAMPLE_THREADS * 8) {
+      const short8v x = *reinterpret_cast<const short8v*>(row + v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned int key = sample_key((unsigned short)x[j]);
+        if (k_on && (key >> 8) == bin_k)
+          atomicAdd(&cnt[(key & 255u) * SAMPLE_COPIES + copy], 1u);
+        if (p_on && (key >> 8) == bin_p) {
+          const float z = bf2f((unsigned short)x[j]);
+          atomicAdd(&mass[(key & 255u) * SAMPLE_COPIES + copy],
+                    sample_mass(expf(z / T - m)));
+        }
+      }
+    }
+    if (k_on) {
+      sample_select(cnt, want_k, sel_k, &above_k, tid);
+      threshold = (bin_k << 8) | sel_k[0];
+    }
+    if (p_on) {
+      sample_select(mass, want_p, sel_p, &above_p, tid);
+      const unsigned int t = (bin_p << 8) | sel_p[0];
+      threshold = t > threshold ? t : threshold;
+    }
+  }
+
+  unsigned int token = max_index;
+  unsigned int kept = 1u;
+  if (sampled) {
+    // pass 4: Gumbel-max over the kept tokens; a Philox block serves
+    // the four tokens 4c .. 4c + 3 and is skipped when none is kept
+    const unsigned long long sd = (unsigned long long)seed[b];
+    const uint32_t key0 = (uint32_t)sd, key1 = (uint32_t)(sd >> 32);
+    unsigned long long top = 0ull;
+    kept = 0u;
+    for (int v = tid * 8; v < V; v += SAMPLE_THREADS * 8) {
+      const short8v x = *reinterpret_cast<const short8v*>(row + v);
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        bool keep[4];
+        float s[4];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned short raw = (unsigned short)x[half * 4 + j];
+          s[j] = bf2f(raw) / T;
+          keep[j] = sample_key(raw) >= threshold;
+          if (mp_on && keep[j])
+            keep[j] = (double)sample_mass(expf(s[j] - m)) >= mp_bound;
+          any = any || keep[j];
+        }
+        if (!any) continue;
+        uint32_t r[4];
+        philox4x32_10((uint32_t)(v >> 2) + half, (uint32_t)position, 0u, 0u,
+                      key0, key1, r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (!keep[j]) continue;
+          ++kept;
+          const float score = s[j] + sample_gumbel(r[j]);
+          const unsigned long long packed = sample_pack(
+              sample_f32_ordered(score), (unsigned)(v + half * 4 + j));
+          top = packed > top ? packed : top;
+        }
+      }
+    }
+    top = sample_block_max(top, red64, tid);
+    kept = (unsigned int)sample_block_sum(kept, red64, tid);
+    token = 0xFFFFFFFFu - (unsigned int)top;
+    if (kept == 0u || token >= (unsigned int)V) {  // nothing kept: argmax
+      token = max_index;
+      kept = 1u;
+    }
+  }
+  if (tid == 0) {
+    out_tokens[b] = (long long)token;
+    if (out_kept) out_kept[b] = (int)kept;
+    if (out_logprob)
+      out_logprob[b] = (bf2f(row[token]) - zmax) - logf(lsum);
+  }
+}
+
+void launch_sample_tokens(const void* logits, const void* pos,
+                          const void* temperature, const void* top_k,
+                          const void* top_p, const void* min_p,
+                          const void* seed, void* out_tokens,
+                          void* out_logprob, void* out_kept, int B, int V,
+                          void* stream) {
+  if (B <= 0 || V <= 0) return;
+  hipLaunchKernelGGL(sample_tokens_kernel, dim3(B), dim3(SAMPLE_THREADS), 0,
+                     (hipStream_t)stream, (const unsigned short*)logits,
+                     (const int*)pos, (const float*)temperature,
+                     (const int*)top_k, (const float*)top_p,
+                     (const float*)min_p, (const long long*)seed,
+                     (long long*)out_tokens, (float*)out_logprob,
+                     (int*)out_kept, V);
+}
+
+// ---------------------------------------------------------------------
 // Row softmax (bf16 in/out, online single pass over LDS-staged row,
 // used by classic-model servers & tests)
 // ---------------------------------------------------------------------
