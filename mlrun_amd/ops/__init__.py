@@ -169,11 +169,18 @@ _GEMM_PLAN_TABLE = {
     # picks cells that regress the bench by ~6% (in-graph execution
     # state differs: back-to-back kernels, dirty L2, sustained clocks).
     # Three e2e A/Bs confirmed this table; treat e2e as ground truth.
-    (6144, 4096): (4, 2),     # qkv (ks4: 768 WGs vs 192 — re-tuned
+    # Variant 4 = LDS-DMA operand rings (batch 17..32; other batch
+    # sizes run variant 1's kernels).  All four projections moved from
+    # variant 2 at UNCHANGED ksplit, so outputs are bit-identical:
+    # e2e 149.2 -> 191.8 req/s (medians of 3 alternating runs); every
+    # shape gains alone except qkv (neutral alone, +1.3% on top of the
+    # other three).  ksplit re-tunes at variant 4 (qkv 2, wo 1/4,
+    # gate|up 2, down 2/8) were all within +-1.5% or worse: not taken.
+    (6144, 4096): (4, 4),     # qkv (ks4: 768 WGs vs 192 — re-tuned
     #   after the attention/LDS round; e2e 126.4 -> 127.9 req/s)
-    (4096, 4096): (2, 2),     # wo
-    (28672, 4096): (1, 2),    # gate|up
-    (4096, 14336): (4, 2),    # down
+    (4096, 4096): (2, 4),     # wo
+    (28672, 4096): (1, 4),    # gate|up
+    (4096, 14336): (4, 4),    # down
     (128256, 4096): (1, 0),   # lm_head
 }
 

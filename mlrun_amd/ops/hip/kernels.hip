@@ -20,8 +20,11 @@
 
 #include <hip/hip_fp8.h>
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cfloat>
 #include <cstdint>
+#include <cstring>
+#include <mutex>
 
 #include "kernels.h"
 
@@ -696,6 +699,250 @@ __global__ __launch_bounds__(256) void skinny_gemm_ws_pipe_kernel(
   }
 }
 
+// LDS-DMA ring variant of skinny_gemm_ws_pipe_kernel<SPLIT, 2, *, 2>
+// (docs/kernels.md "LDS-DMA operand rings"): same decomposition, same
+// per-wave [kbegin, kend), same 32-k step order and MFMA operand map,
+// so its results are bit-identical; only the way the operands reach
+// the MFMA differs.  Every wave owns DEPTH private LDS slots; a slot
+// holds one stage = STAGE_K columns of the wave's 32 weight rows and
+// of the 32 A rows.  Both are filled by global_load_lds_dwordx4 (W
+// with nt, A cached), so bytes in flight cost LDS instead of VGPRs and
+// one wave-instruction fetches whole STAGE_K*2-byte row segments
+// (>= one 128-B line per row).  No other wave touches a wave's slots:
+// the K-loop has no workgroup barrier, only hand-counted vmcnt waits.
+//
+// LDS image of one operand tile: row-major [32][STAGE_K] bf16; one DMA
+// instruction writes 1 KiB lane-linearly = 1024/(2*STAGE_K) whole
+// rows.  The 16-B chunks of a row are XOR-permuted on the SOURCE
+// address (inside the row's contiguous segment) and the same XOR is
+// applied to the read address, which makes the ds_read_b128 fragment
+// reads (16 rows x one chunk per 16-lane group) conflict-free.
+template <int STAGE_K>
+DEV int lds_ring_swz(int row) {
+  // 128-B rows: two rows share a 256-B bank row -> 8 chunk positions
+  // per row, keyed by row>>1; 256-B rows: 16 positions keyed by row
+  return STAGE_K == 64 ? ((row >> 1) & 7) : (row & 15);
+}
+
+template <int N>
+DEV void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+typedef __attribute__((address_space(3))) void* lds_void_ptr;
+
+template <bool SPLIT, int STAGE_K, int DEPTH>
+__global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
+    void* __restrict__ out, const unsigned short* __restrict__ A,
+    const unsigned short* __restrict__ W, int M, int N, int K, int ksplit) {
+  constexpr int MT = 2, NT = 32;
+  constexpr int ROW_B = STAGE_K * 2;       // bytes of one row per stage
+  constexpr int OP_B = 32 * ROW_B;         // one operand tile
+  constexpr int SLOT_B = 2 * OP_B;         // W tile then A tile
+  constexpr int WAVE_B = DEPTH * SLOT_B;   // a wave's private ring
+  constexpr int LPR = ROW_B / 16;          // lanes (chunks) per row
+  constexpr int RPI = 64 / LPR;            // rows per DMA instruction
+  constexpr int NDMA_OP = 32 / RPI;        // DMA instructions per tile
+  constexpr int NDMA = 2 * NDMA_OP;        // ... per stage
+  constexpr int SPS = STAGE_K / 32;        // 32-k steps per stage
+  static_assert(WAVE_B >= 4 * 16 * MT * NT, "comb aliases the ring");
+  extern __shared__ __attribute__((aligned(1024))) unsigned char lds_ring[];
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n0 = blockIdx.x * NT;
+  if (n0 >= N) return;
+  int cbegin = 0, cend = K;
+  if (SPLIT) {
+    const int kchunk = (K / ksplit + 31) & ~31;
+    cbegin = blockIdx.y * kchunk;
+    cend = cbegin + kchunk;
+    if (cend > K) cend = K;
+  }
+  const int clen = cend - cbegin;
+  const int per_wave = ((clen / 4) + 31) & ~31;
+  int kbegin = cbegin + wave * per_wave;
+  int kend = kbegin + per_wave;
+  if (kend > cend) kend = cend;
+  // whole stages go through the ring; an empty or short range runs none
+  const int nst = kend > kbegin ? (kend - kbegin) / STAGE_K : 0;
+
+  f32x4v acc0[MT], acc1[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    acc0[t] = {0.f, 0.f, 0.f, 0.f};
+    acc1[t] = {0.f, 0.f, 0.f, 0.f};
+  }
+
+  // DMA source: instruction i, lane l -> tile row i*RPI + l/LPR, LDS
+  // chunk position l%LPR, which receives source chunk pos ^ swz(row).
+  // Rows past N-1 / M-1 are clamped, chunks stay inside the stage.
+  const unsigned short* wsrc[NDMA_OP];
+  const unsigned short* asrc[NDMA_OP];
+#pragma unroll
+  for (int i = 0; i < NDMA_OP; ++i) {
+    const int row = i * RPI + lane / LPR;
+    const int chunk = (lane % LPR) ^ lds_ring_swz<STAGE_K>(row);
+    wsrc[i] = W + (size_t)min(n0 + row, N - 1) * K + kbegin + chunk * 8;
+    asrc[i] = A + (size_t)min(row, M - 1) * K + kbegin + chunk * 8;
+  }
+  // fragment read: lane l holds row l&15, source chunk (l>>4) + 4*step
+  unsigned char* const ring = lds_ring + wave * WAVE_B;
+  int rd_off[SPS];
+#pragma unroll
+  for (int s = 0; s < SPS; ++s) {
+    const int row = lane & 15;
+    rd_off[s] = row * ROW_B +
+                ((((lane >> 4) + 4 * s) ^ lds_ring_swz<STAGE_K>(row)) << 4);
+  }
+
+  auto issue = [&](int stage, int slot) {
+    unsigned char* dst = ring + slot * SLOT_B;
+    const int koff = stage * STAGE_K;
+    // (the host pass cannot type-check the DMA builtin)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int i = 0; i < NDMA_OP; ++i)
+      __builtin_amdgcn_global_load_lds(wsrc[i] + koff,
+                                       (lds_void_ptr)(dst + i * 1024), 16,
+                                       0, 2);  // nt: read once per step
+#pragma unroll
+    for (int i = 0; i < NDMA_OP; ++i)
+      __builtin_amdgcn_global_load_lds(asrc[i] + koff,
+                                       (lds_void_ptr)(dst + OP_B + i * 1024),
+                                       16, 0, 0);
+#else
+    (void)dst;
+    (void)koff;
+#endif
+  };
+  // consume slot `slot`; refill it with stage `refill` (< 0: none) once
+  // its fragments sit in registers
+  auto consume = [&](int slot, int refill) {
+    const unsigned char* src = ring + slot * SLOT_B;
+    short8v bf0[SPS], bf1[SPS], af[SPS][MT];
+#pragma unroll
+    for (int s = 0; s < SPS; ++s) {
+      bf0[s] = *reinterpret_cast<const short8v*>(src + rd_off[s]);
+      bf1[s] =
+          *reinterpret_cast<const short8v*>(src + rd_off[s] + 16 * ROW_B);
+#pragma unroll
+      for (int t = 0; t < MT; ++t)
+        af[s][t] = *reinterpret_cast<const short8v*>(
+            src + OP_B + rd_off[s] + 16 * t * ROW_B);
+    }
+    // the reads must have returned before a DMA may overwrite the slot
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (refill >= 0) issue(refill, slot);
+#pragma unroll
+    for (int s = 0; s < SPS; ++s)
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            af[s][t], bf0[s], acc0[t], 0, 0, 0);
+        acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            af[s][t], bf1[s], acc1[t], 0, 0, 0);
+      }
+  };
+
+#pragma unroll
+  for (int s = 0; s < DEPTH; ++s)
+    if (s < nst) issue(s, s);
+  int j = 0, slot = 0;
+  // steady state: DEPTH-1 younger stages stay in flight behind stage j
+  for (; j + DEPTH < nst; ++j) {
+    wait_vmcnt<NDMA*(DEPTH - 1)>();
+    consume(slot, j + DEPTH);
+    slot = slot + 1 == DEPTH ? 0 : slot + 1;
+  }
+  // drain: nst - j <= DEPTH stages are left and all of them are issued
+  static_assert(DEPTH == 2 || DEPTH == 3, "drain is written for 2 and 3");
+  if (DEPTH == 3 && nst - j == 3) {
+    wait_vmcnt<2 * NDMA>();
+    consume(slot, -1);
+    slot = slot + 1 == DEPTH ? 0 : slot + 1;
+    ++j;
+  }
+  if (nst - j == 2) {
+    wait_vmcnt<NDMA>();
+    consume(slot, -1);
+    slot = slot + 1 == DEPTH ? 0 : slot + 1;
+    ++j;
+  }
+  if (nst - j == 1) {
+    wait_vmcnt<0>();
+    consume(slot, -1);
+  }
+
+  // the rest of the range (< STAGE_K, a multiple of 32) as plain 32-k
+  // steps; no DMA is pending here, so ordinary loads wait normally
+  if (kend > kbegin) {
+    const int arow = lane & 15;
+    const int kb = (lane >> 4) * 8;
+    const unsigned short* aptr0 = A + (size_t)min(arow, M - 1) * K + kb;
+    const unsigned short* aptr1 =
+        A + (size_t)min(arow + 16, M - 1) * K + kb;
+    const unsigned short* bptr0 =
+        W + (size_t)min(n0 + arow, N - 1) * K + kb;
+    const unsigned short* bptr1 =
+        W + (size_t)min(n0 + arow + 16, N - 1) * K + kb;
+    for (int k = kbegin + nst * STAGE_K; k < kend; k += 32) {
+      short8v bf0 = *reinterpret_cast<const short8v*>(bptr0 + k);
+      short8v bf1 = *reinterpret_cast<const short8v*>(bptr1 + k);
+      short8v af0 = *reinterpret_cast<const short8v*>(aptr0 + k);
+      short8v af1 = *reinterpret_cast<const short8v*>(aptr1 + k);
+      acc0[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af0, bf0, acc0[0],
+                                                        0, 0, 0);
+      acc1[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af0, bf1, acc1[0],
+                                                        0, 0, 0);
+      acc0[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af1, bf0, acc0[1],
+                                                        0, 0, 0);
+      acc1[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af1, bf1, acc1[1],
+                                                        0, 0, 0);
+    }
+  }
+
+  // fold through LDS: a wave's partial goes to the head of its OWN
+  // drained ring, so no barrier is needed before these writes
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  typedef float comb_t[16 * MT][NT];
+  comb_t& mine = *reinterpret_cast<comb_t*>(ring);
+  const int crow_base = (lane >> 4) * 4;
+  const int ccol = lane & 15;
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      mine[16 * t + crow_base + r][ccol] = acc0[t][r];
+      mine[16 * t + crow_base + r][ccol + 16] = acc1[t][r];
+    }
+  __syncthreads();
+  if (wave == 0) {
+    const comb_t& c0 = *reinterpret_cast<const comb_t*>(lds_ring);
+    const comb_t& c1 = *reinterpret_cast<const comb_t*>(lds_ring + WAVE_B);
+    const comb_t& c2 =
+        *reinterpret_cast<const comb_t*>(lds_ring + 2 * WAVE_B);
+    const comb_t& c3 =
+        *reinterpret_cast<const comb_t*>(lds_ring + 3 * WAVE_B);
+    constexpr int CPL = 4 * MT * 2;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+      const int cell = lane * CPL + c;
+      const int m = cell / NT;
+      const int n = cell % NT;
+      if (m >= M || n0 + n >= N) continue;
+      float sum = c0[m][n] + c1[m][n] + c2[m][n] + c3[m][n];
+      if (SPLIT) {
+        float* part = (float*)out + (size_t)blockIdx.y * M * N;
+        part[(size_t)m * N + n0 + n] = sum;
+      } else {
+        ((unsigned short*)out)[(size_t)m * N + n0 + n] = f2bf(sum);
+      }
+    }
+  }
+}
+
 __global__ void reduce_cast_kernel(unsigned short* __restrict__ out,
                                    const float* __restrict__ part,
                                    long long mn, int ksplit);
@@ -997,13 +1244,99 @@ static bool launch_pipe_mt2(void* out, const void* A, const void* W,
   return true;
 }
 
+// MLRUN_GEMM_LDS_RING=64x2|64x3|128x2 selects the (STAGE_K, DEPTH) ring
+// of the variant-4 LDS-DMA kernel: 64, 96 or 128 KiB of LDS per
+// workgroup.  Read once.  Default 64x2: two workgroups fit a CU, and it
+// won the end-to-end A/B (profiles/README.md, "LDS-DMA operand rings").
+static int gemm_lds_ring_env() {
+  static int v = [] {
+    const char* e = getenv("MLRUN_GEMM_LDS_RING");
+    if (e && !strcmp(e, "64x3")) return 1;
+    if (e && !strcmp(e, "128x2")) return 2;
+    return 0;  // 64x2
+  }();
+  return v;
+}
+
+typedef void (*lds_ring_kern_t)(void*, const unsigned short*,
+                                const unsigned short*, int, int, int, int);
+
+template <int STAGE_K, int DEPTH>
+constexpr int lds_ring_bytes() {
+  return 4 * DEPTH * 2 * 32 * STAGE_K * 2;
+}
+
+// The rings need more dynamic LDS than the 64 KiB a kernel gets by
+// default.  The first variant-4 call on a device raises the limit of
+// all six instantiations under a lock, so engine replicas that start
+// on several threads at once never change a kernel's attributes while
+// another thread launches it.  This is not a stream operation; the
+// first call is expected outside graph capture (engines warm up
+// eagerly before they capture).
+static void lds_ring_allow_all() {
+  static std::mutex mu;
+  static std::atomic<bool> done[16];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+  if (done[dev].load(std::memory_order_acquire)) return;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done[dev].load(std::memory_order_relaxed)) return;
+  const struct { lds_ring_kern_t kern; int bytes; } all[] = {
+      {skinny_gemm_ws_lds_kernel<false, 64, 2>, lds_ring_bytes<64, 2>()},
+      {skinny_gemm_ws_lds_kernel<true, 64, 2>, lds_ring_bytes<64, 2>()},
+      {skinny_gemm_ws_lds_kernel<false, 64, 3>, lds_ring_bytes<64, 3>()},
+      {skinny_gemm_ws_lds_kernel<true, 64, 3>, lds_ring_bytes<64, 3>()},
+      {skinny_gemm_ws_lds_kernel<false, 128, 2>, lds_ring_bytes<128, 2>()},
+      {skinny_gemm_ws_lds_kernel<true, 128, 2>, lds_ring_bytes<128, 2>()},
+  };
+  for (const auto& k : all)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.kern),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              k.bytes);
+  done[dev].store(true, std::memory_order_release);
+}
+
+template <bool SPLIT, int STAGE_K, int DEPTH>
+static void launch_lds_ring(void* out, const void* A, const void* W, int M,
+                            int N, int K, int ksplit, const dim3& grid,
+                            void* stream) {
+  lds_ring_kern_t kern = skinny_gemm_ws_lds_kernel<SPLIT, STAGE_K, DEPTH>;
+  constexpr int bytes = lds_ring_bytes<STAGE_K, DEPTH>();
+  lds_ring_allow_all();
+  hipLaunchKernelGGL(kern, grid, dim3(256), bytes, (hipStream_t)stream, out,
+                     (const unsigned short*)A, (const unsigned short*)W, M,
+                     N, K, ksplit);
+}
+
+// variant 4, 16 < M <= 32
+template <bool SPLIT>
+static void launch_lds_mt2(void* out, const void* A, const void* W, int M,
+                           int N, int K, int ksplit, const dim3& grid,
+                           void* stream) {
+  switch (gemm_lds_ring_env()) {
+    case 1:
+      launch_lds_ring<SPLIT, 64, 3>(out, A, W, M, N, K, ksplit, grid,
+                                    stream);
+      break;
+    case 2:
+      launch_lds_ring<SPLIT, 128, 2>(out, A, W, M, N, K, ksplit, grid,
+                                     stream);
+      break;
+    default:
+      launch_lds_ring<SPLIT, 64, 2>(out, A, W, M, N, K, ksplit, grid,
+                                    stream);
+  }
+}
+
 void launch_skinny_gemm_slabs(void* part_f32, const void* A, const void* W,
                               int M, int N, int K, int ksplit, int variant,
                               void* stream) {
   const int nblocks = variant == 3 ? (N + 15) / 16
                       : variant >= 1 ? (N + 31) / 32 : (N + 127) / 128;
   const dim3 grid(nblocks, ksplit);
-  if (variant == 3) {
+  if (variant == 4 && M > 16 && M <= 32) {
+    launch_lds_mt2<true>(part_f32, A, W, M, N, K, ksplit, grid, stream);
+  } else if (variant == 3) {
     // 16-wide n-tiles: 2x the workgroups at unchanged per-wave K
     if (M > 32)
       hipLaunchKernelGGL((skinny_gemm_ws_kernel<true, 4, 4, 1>), grid,
@@ -1068,7 +1401,10 @@ void launch_skinny_gemm(void* out_bf16, void* part_f32, const void* A,
   const int nblocks = variant == 3 ? (N + 15) / 16
                       : variant >= 1 ? (N + 31) / 32 : (N + 127) / 128;
   if (ksplit == 1) {
-    if (variant == 3) {
+    if (variant == 4 && M > 16 && M <= 32) {
+      launch_lds_mt2<false>(out_bf16, A, W, M, N, K, 1, dim3(nblocks),
+                            stream);
+    } else if (variant == 3) {
       if (M > 32)
         hipLaunchKernelGGL((skinny_gemm_ws_kernel<false, 4, 4, 1>),
                            dim3(nblocks), dim3(256), 0,
