@@ -20,6 +20,7 @@ Design (MI355X-first, not a port — the reference has no model code):
 """
 
 import math
+import os
 import typing
 from dataclasses import dataclass
 
@@ -441,8 +442,7 @@ class LlamaDecodeEngine:
         # wins >=10% only at S>=1024 but costs 2.4% on the headline
         # (S~160).  Long-context deployments: pass seq_len to
         # pick_attn_nsplit / set MLRUN_ATTN_NSPLIT.
-        import os as _os
-        _ns = _os.environ.get("MLRUN_ATTN_NSPLIT")
+        _ns = os.environ.get("MLRUN_ATTN_NSPLIT")
         self.attn_nsplit = int(_ns) if _ns else \
             ops.pick_attn_nsplit(B, w.hkv)
         self.buf_attn_ws = torch.empty(
@@ -715,9 +715,7 @@ class LlamaDecodeEngine:
         # net loss (consumer grid = B rows is parallelism-starved vs the
         # 2048-block reduce_cast), so only the rope/KV consumer (grid
         # B x heads) fuses by default; override with MLRUN_SLAB_MODE.
-        import os as _os
-
-        mode = _os.environ.get("MLRUN_SLAB_MODE", "rope")
+        mode = os.environ.get("MLRUN_SLAB_MODE", "rope")
         on = self.on_gpu and self.tp_size == 1 and mode != "none"
         use_slabs = on and self.weight_dtype == "bf16" and \
             self.kv_dtype == "bf16"  # qkv slab (bf16 caches only)
@@ -727,14 +725,14 @@ class LlamaDecodeEngine:
             # the adapter delta has to land on the bf16 GEMM output
             # before rope / norm: the slab-fused consumers are bypassed
             use_slabs = use_norm_slabs = False
+        if use_slabs or use_norm_slabs:
+            from mlrun_amd import _hip_ops
         for li, layer in enumerate(w.layers):
             # qkv projection -> rope -> caches
             done = 0
             if use_slabs:
                 done = self._gemm_slabs(self.buf_hidden, layer["wqkv"])
                 if done:
-                    from mlrun_amd import _hip_ops
-
                     _hip_ops.rope_kv_slab(
                         self.buf_qkv, self.k_cache[li], self.v_cache[li],
                         self.buf_c32, positions, self.cos_sin, w.hq, done)
@@ -762,8 +760,6 @@ class LlamaDecodeEngine:
             if use_norm_slabs:
                 done = self._gemm_slabs(self.buf_attn_out, layer["wo"])
                 if done:
-                    from mlrun_amd import _hip_ops
-
                     _hip_ops.fused_add_rmsnorm_slab(
                         self.buf_hidden, self.buf_residual, self.buf_c32,
                         layer["ffn_norm"], done, cfg.rms_eps)
@@ -782,8 +778,6 @@ class LlamaDecodeEngine:
             if use_norm_slabs:
                 done = self._gemm_slabs(self.buf_hidden, layer["wgu"])
                 if done:
-                    from mlrun_amd import _hip_ops
-
                     _hip_ops.swiglu_slab(self.buf_act, self.buf_c32, done)
             if not done:
                 self._gemm(self.buf_hidden, layer["wgu"], self.buf_gu,
@@ -798,8 +792,6 @@ class LlamaDecodeEngine:
             if use_norm_slabs:
                 done = self._gemm_slabs(self.buf_act, layer["wdown"])
                 if done:
-                    from mlrun_amd import _hip_ops
-
                     _hip_ops.fused_add_rmsnorm_slab(
                         self.buf_hidden, self.buf_residual, self.buf_c32,
                         next_norm, done, cfg.rms_eps)
@@ -963,28 +955,54 @@ class LlamaDecodeEngine:
             raise ValueError(
                 f"token id outside [0, {self.cfg.vocab_size}) in prompt")
 
-    @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, adapters=None
-                ) -> torch.Tensor:
-        """Process prompts [B, S]; fill KV caches; return last-token
-        logits [B, vocab].  hipBLASLt GEMMs + SDPA.  ``adapters``: one
-        LoRA table slot per prompt (-1 = base model, the default); the
-        ids stay in buf_adapter for the decode steps that follow."""
+    def _run_layers(self, residual, project, attend):
+        """The layer loop of every non-graph pass (the three prefills
+        and verify_step) over the token rows ``residual`` [T, H], which
+        it updates in place; returns the final normed hidden [T, H].
+        ``project(li, name, x)`` is the GEMM of x with layer li's weight
+        ``name`` plus whatever delta the path adds; ``attend(li, qkv)``
+        writes the layer's KV rows and returns the attention output
+        [T, Hq*d]."""
         cfg, w = self.cfg, self.weights
-        B, S = tokens.shape
-        d = cfg.head_dim
-        self._check_token_ids(tokens)
-        plan = self._adapter_plan(adapters, slice(0, B), [S] * B)
-        tokens = tokens.to(self.device)
-        x = w.embed[tokens.reshape(-1)]  # [B*S, H]
-        residual = x.contiguous()
-        positions = torch.arange(S, dtype=torch.int32, device=self.device
-                                 ).repeat(B)
         hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
                              eps=cfg.rms_eps)
         for li, layer in enumerate(w.layers):
-            qkv = self._lora_prefill(plan, li, "wqkv", hidden,
-                                     hidden @ layer["wqkv"].t())
+            attn = attend(li, project(li, "wqkv", hidden))
+            proj = project(li, "wo", attn)
+            self._maybe_allreduce(proj)
+            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
+                                           residual=residual,
+                                           eps=cfg.rms_eps)
+            gu = project(li, "wgu", hidden)
+            act = ops.swiglu_fused(gu.contiguous())
+            down = project(li, "wdown", act)
+            self._maybe_allreduce(down)
+            next_norm = w.layers[li + 1]["attn_norm"] \
+                if li + 1 < cfg.num_layers else w.final_norm
+            hidden = ops.fused_add_rmsnorm(down, next_norm,
+                                           residual=residual,
+                                           eps=cfg.rms_eps)
+        return hidden
+
+    def _prefill_project(self, plan):
+        """_run_layers' ``project`` of the prefills: the library GEMM
+        plus the LoRA deltas of ``plan``."""
+        layers = self.weights.layers
+
+        def project(li, name, x):
+            return self._lora_prefill(plan, li, name, x,
+                                      x @ layers[li][name].t())
+        return project
+
+    def _dense_attend(self, rows, B, S):
+        """_run_layers' ``attend`` of the dense prefills: B prompts of S
+        tokens each, rope, K/V into cache rows ``rows`` (an index for
+        the cache's batch dimension), causal SDPA."""
+        w, d = self.weights, self.cfg.head_dim
+        positions = torch.arange(S, dtype=torch.int32, device=self.device
+                                 ).repeat(B)
+
+        def attend(li, qkv):
             q = qkv[:, :w.hq * d].reshape(B * S, w.hq, d).contiguous()
             k = qkv[:, w.hq * d:(w.hq + w.hkv) * d].reshape(
                 B * S, w.hkv, d).contiguous()
@@ -996,34 +1014,49 @@ class LlamaDecodeEngine:
             if self.kv_dtype == "fp8":
                 k8, ks = ops.quantize_kv_rows(kc)
                 v8, vs = ops.quantize_kv_rows(vc)
-                self.k_cache[li, :, :, :S] = k8
-                self.v_cache[li, :, :, :S] = v8
-                self.k_scale[li, :, :, :S] = ks
-                self.v_scale[li, :, :, :S] = vs
+                self.k_cache[li, rows, :, :S] = k8
+                self.v_cache[li, rows, :, :S] = v8
+                self.k_scale[li, rows, :, :S] = ks
+                self.v_scale[li, rows, :, :S] = vs
             else:
-                self.k_cache[li, :, :, :S] = kc
-                self.v_cache[li, :, :, :S] = vc
+                self.k_cache[li, rows, :, :S] = kc
+                self.v_cache[li, rows, :, :S] = vc
             qh = q.view(B, S, w.hq, d).transpose(1, 2)
             attn = torch.nn.functional.scaled_dot_product_attention(
                 qh, kc, vc, is_causal=True, enable_gqa=True)
-            attn = attn.transpose(1, 2).reshape(B * S, w.hq * d)
-            proj = self._lora_prefill(plan, li, "wo", attn,
-                                      attn @ layer["wo"].t())
-            self._maybe_allreduce(proj)
-            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
-            gu = self._lora_prefill(plan, li, "wgu", hidden,
-                                    hidden @ layer["wgu"].t())
-            act = ops.swiglu_fused(gu.contiguous())
-            down = self._lora_prefill(plan, li, "wdown", act,
-                                      act @ layer["wdown"].t())
-            self._maybe_allreduce(down)
-            next_norm = w.layers[li + 1]["attn_norm"] \
-                if li + 1 < cfg.num_layers else w.final_norm
-            hidden = ops.fused_add_rmsnorm(down, next_norm,
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
+            return attn.transpose(1, 2).reshape(B * S, w.hq * d)
+        return attend
+
+    def _first_tokens(self, logits, slots):
+        """First token of the freshly prefilled ``slots`` (a long
+        tensor) into buf_tokens, from their last-token logits."""
+        if self.sampling == "request":
+            self._sample_slots(logits, slots)
+        elif self.per_slot_temp:
+            scores = logits.float() / self.buf_temp[slots]
+            u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
+            self.buf_tokens[slots] = (
+                scores - torch.log(-torch.log(u))).argmax(dim=-1)
+        else:
+            self.buf_tokens[slots] = self._select_tokens(logits)
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, adapters=None
+                ) -> torch.Tensor:
+        """Process prompts [B, S]; fill KV caches; return last-token
+        logits [B, vocab].  hipBLASLt GEMMs + SDPA.  ``adapters``: one
+        LoRA table slot per prompt (-1 = base model, the default); the
+        ids stay in buf_adapter for the decode steps that follow."""
+        w = self.weights
+        B, S = tokens.shape
+        self._check_token_ids(tokens)
+        plan = self._adapter_plan(adapters, slice(0, B), [S] * B)
+        tokens = tokens.to(self.device)
+        x = w.embed[tokens.reshape(-1)]  # [B*S, H]
+        # K/V fill the cache's whole batch dimension
+        hidden = self._run_layers(x.contiguous(),
+                                  self._prefill_project(plan),
+                                  self._dense_attend(slice(None), B, S))
         self.cache_lens.fill_(S)
         last = hidden.view(B, S, -1)[:, -1]
         logits = last @ w.lm_head.t()
@@ -1066,68 +1099,15 @@ class LlamaDecodeEngine:
         assert S < cfg.max_seq_len
         self._check_token_ids(tokens)
         plan = self._adapter_plan(adapters, slots, [S] * Bp)
-        d = cfg.head_dim
         tokens = tokens.to(self.device)
         x = w.embed[tokens.reshape(-1)]
-        residual = x.contiguous()
-        positions = torch.arange(S, dtype=torch.int32,
-                                 device=self.device).repeat(Bp)
-        hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
-                             eps=cfg.rms_eps)
-        for li, layer in enumerate(w.layers):
-            qkv = self._lora_prefill(plan, li, "wqkv", hidden,
-                                     hidden @ layer["wqkv"].t())
-            q = qkv[:, :w.hq * d].reshape(Bp * S, w.hq, d).contiguous()
-            k = qkv[:, w.hq * d:(w.hq + w.hkv) * d].reshape(
-                Bp * S, w.hkv, d).contiguous()
-            v = qkv[:, (w.hq + w.hkv) * d:].reshape(Bp * S, w.hkv, d)
-            ops.rope_inplace(q, positions, self.cos_sin)
-            ops.rope_inplace(k, positions, self.cos_sin)
-            kc = k.view(Bp, S, w.hkv, d).transpose(1, 2).contiguous()
-            vc = v.view(Bp, S, w.hkv, d).transpose(1, 2).contiguous()
-            if self.kv_dtype == "fp8":
-                k8, ks = ops.quantize_kv_rows(kc)
-                v8, vs = ops.quantize_kv_rows(vc)
-                self.k_cache[li, slots, :, :S] = k8
-                self.v_cache[li, slots, :, :S] = v8
-                self.k_scale[li, slots, :, :S] = ks
-                self.v_scale[li, slots, :, :S] = vs
-            else:
-                self.k_cache[li, slots, :, :S] = kc
-                self.v_cache[li, slots, :, :S] = vc
-            qh = q.view(Bp, S, w.hq, d).transpose(1, 2)
-            attn = torch.nn.functional.scaled_dot_product_attention(
-                qh, kc, vc, is_causal=True, enable_gqa=True)
-            attn = attn.transpose(1, 2).reshape(Bp * S, w.hq * d)
-            proj = self._lora_prefill(plan, li, "wo", attn,
-                                      attn @ layer["wo"].t())
-            self._maybe_allreduce(proj)
-            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
-            gu = self._lora_prefill(plan, li, "wgu", hidden,
-                                    hidden @ layer["wgu"].t())
-            act = ops.swiglu_fused(gu.contiguous())
-            down = self._lora_prefill(plan, li, "wdown", act,
-                                      act @ layer["wdown"].t())
-            self._maybe_allreduce(down)
-            next_norm = w.layers[li + 1]["attn_norm"] \
-                if li + 1 < cfg.num_layers else w.final_norm
-            hidden = ops.fused_add_rmsnorm(down, next_norm,
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
+        hidden = self._run_layers(x.contiguous(),
+                                  self._prefill_project(plan),
+                                  self._dense_attend(slots, Bp, S))
         self.cache_lens[slots] = S
         last = hidden.view(Bp, S, -1)[:, -1]
         logits = last @ w.lm_head.t()
-        if self.sampling == "request":
-            self._sample_slots(logits, slots)
-        elif self.per_slot_temp:
-            scores = logits.float() / self.buf_temp[slots]
-            u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
-            self.buf_tokens[slots] = (
-                scores - torch.log(-torch.log(u))).argmax(dim=-1)
-        else:
-            self.buf_tokens[slots] = self._select_tokens(logits)
+        self._first_tokens(logits, slots)
         return logits
 
     @torch.no_grad()
@@ -1197,49 +1177,23 @@ class LlamaDecodeEngine:
         max_q_len = max(lens)
         plan = self._adapter_plan(adapters, slots_i32.long(), lens)
         x = w.embed[tokens]  # [T, H]
-        residual = x.contiguous()
-        hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
-                             eps=cfg.rms_eps)
-        for li, layer in enumerate(w.layers):
-            qkv = self._lora_prefill(plan, li, "wqkv", hidden,
-                                     hidden @ layer["wqkv"].t())
+
+        def attend(li, qkv):
             ops.rope_kv_varlen(qkv, self.k_cache[li], self.v_cache[li],
                                positions, tok_slot, self.cos_sin, w.hq)
             q = qkv[:, :w.hq * d].view(T, w.hq, d)  # strided view
-            attn = ops.attn_prefill(q, self.k_cache[li], self.v_cache[li],
+            return ops.attn_prefill(q, self.k_cache[li], self.v_cache[li],
                                     cu_seqlens, slots_i32, kv_start,
                                     self.scale, max_q_len=max_q_len)
-            proj = self._lora_prefill(plan, li, "wo", attn,
-                                      attn @ layer["wo"].t())
-            self._maybe_allreduce(proj)
-            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
-            gu = self._lora_prefill(plan, li, "wgu", hidden,
-                                    hidden @ layer["wgu"].t())
-            act = ops.swiglu_fused(gu.contiguous())
-            down = self._lora_prefill(plan, li, "wdown", act,
-                                      act @ layer["wdown"].t())
-            self._maybe_allreduce(down)
-            next_norm = w.layers[li + 1]["attn_norm"] \
-                if li + 1 < cfg.num_layers else w.final_norm
-            hidden = ops.fused_add_rmsnorm(down, next_norm,
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
+
+        hidden = self._run_layers(x.contiguous(),
+                                  self._prefill_project(plan), attend)
         slots_long = slots_i32.long()
         self.cache_lens[slots_long] = kv_start + (
             cu_seqlens[1:] - cu_seqlens[:-1])
         last = hidden[cu_seqlens[1:].long() - 1]
         logits = last @ w.lm_head.t()
-        if self.sampling == "request":
-            self._sample_slots(logits, slots_long)
-        elif self.per_slot_temp:
-            scores = logits.float() / self.buf_temp[slots_long]
-            u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
-            self.buf_tokens[slots_long] = (
-                scores - torch.log(-torch.log(u))).argmax(dim=-1)
-        else:
-            self.buf_tokens[slots_long] = self._select_tokens(logits)
+        self._first_tokens(logits, slots_long)
         return logits
 
     # -------------------------------------------------------- generate
@@ -1355,29 +1309,20 @@ class LlamaDecodeEngine:
             if nsplit > 1 and (ws is None or ws.numel() < need):
                 ws = self._verify_ws = torch.empty(
                     need, dtype=torch.float32, device=self.device)
-        residual = w.embed[tokens.reshape(T)].contiguous()
-        hidden = ops.rmsnorm(residual, w.layers[0]["attn_norm"],
-                             eps=cfg.rms_eps)
-        for li, layer in enumerate(w.layers):
-            qkv = self._verify_gemm(hidden, layer["wqkv"], QL)
+
+        def project(li, name, x):
+            return self._verify_gemm(x, w.layers[li][name], QL)
+
+        def attend(li, qkv):
             ops.rope_kv_varlen(qkv, self.k_cache[li], self.v_cache[li],
                                positions, tok_slot, self.cos_sin, w.hq)
             q = qkv[:, :w.hq * d].view(B, QL, w.hq, d)  # strided view
-            attn = ops.attn_verify(q, self.k_cache[li], self.v_cache[li],
+            return ops.attn_verify(q, self.k_cache[li], self.v_cache[li],
                                    base, self.scale, nsplit=nsplit,
                                    partial_ws=ws)
-            proj = self._verify_gemm(attn, layer["wo"], QL)
-            hidden = ops.fused_add_rmsnorm(proj, layer["ffn_norm"],
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
-            gu = self._verify_gemm(hidden, layer["wgu"], QL)
-            act = ops.swiglu_fused(gu.contiguous())
-            down = self._verify_gemm(act, layer["wdown"], QL)
-            next_norm = w.layers[li + 1]["attn_norm"] \
-                if li + 1 < cfg.num_layers else w.final_norm
-            hidden = ops.fused_add_rmsnorm(down, next_norm,
-                                           residual=residual,
-                                           eps=cfg.rms_eps)
+
+        hidden = self._run_layers(w.embed[tokens.reshape(T)].contiguous(),
+                                  project, attend)
         logits = getattr(self, "buf_verify_logits", None)
         if logits is None or logits.shape[1] != QL:
             logits = self.buf_verify_logits = torch.empty(

@@ -5,14 +5,15 @@
 //
 // CDNA4 (gfx950 / MI355X) serving & training kernels.
 //
-// Design notes (see /root/repo/SURVEY.md §2.3/§2.6 — the reference has
+// Design notes (see SURVEY.md §2.3/§2.6 — the reference has
 // no GPU kernels; this kernel surface is defined by the north-star
 // serving/training configs):
 //  - wave = 64 lanes everywhere; all bf16 global loads vectorized as
 //    short8/ushort2 (16B / 4B per lane)
 //  - decode GEMM (M<=16 activations x [N,K] weights) on MFMA
-//    v_mfma_f32_16x16x32_bf16, K-split across workgroups with f32
-//    atomics so the grid fills 256 CUs
+//    v_mfma_f32_16x16x32_bf16, K-split across workgroups so the grid
+//    fills 256 CUs: each split stores its own f32 slab (plain stores)
+//    and reduce_cast or the consumer kernel folds them
 //  - decode attention: one workgroup per (batch, kv-head), one wave
 //    per grouped q-head, online softmax, LDS score buffer
 //  - norm/rope/swiglu fused elementwise kernels at HBM rate
@@ -278,8 +279,8 @@ void launch_silu_mul(void* out, const void* gate, const void* up,
 // Skinny GEMM (decode projections):  C[M,N] (+)= A[M,K] @ W[N,K]^T
 // M <= 16 (decode batch), bf16 inputs, f32 C.
 // MFMA 16x16x32: each wave owns a 32-wide n-tile (2 B-fragments),
-// 4 waves/block -> 128 n per block; K split across gridDim.y with
-// device-scope f32 atomics (cross-XCD safe, guide G12/G16).
+// 4 waves/block -> 128 n per block; K split across gridDim.y, one f32
+// slab per split (SPLIT below).
 // Fragment layout (verified on HW by tests/gpu):
 //   A: lane l holds A[l&15][(l>>4)*8 + j]   j=0..7
 //   B: lane l holds W[n0 + (l&15)][(l>>4)*8 + j] (B^T = W row-major)
@@ -943,9 +944,45 @@ __global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
   }
 }
 
+// fold ksplit partial slabs [ksplit, M, N] f32 -> bf16 [M, N]
 __global__ void reduce_cast_kernel(unsigned short* __restrict__ out,
                                    const float* __restrict__ part,
-                                   long long mn, int ksplit);
+                                   long long mn, int ksplit) {
+  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  long long stride = (long long)gridDim.x * blockDim.x * 4;
+  for (; i + 3 < mn; i += stride) {
+    f32x4v sum = *reinterpret_cast<const f32x4v*>(part + i);
+    for (int s = 1; s < ksplit; ++s) {
+      f32x4v v = *reinterpret_cast<const f32x4v*>(part + (size_t)s * mn + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sum[j] += v[j];
+    }
+    unsigned short o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = f2bf(sum[j]);
+    *reinterpret_cast<uint64_t*>(out + i) =
+        *reinterpret_cast<const uint64_t*>(o);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (long long t = (mn & ~3LL); t < mn; ++t) {
+      float sum = part[t];
+      for (int s = 1; s < ksplit; ++s) sum += part[(size_t)s * mn + t];
+      out[t] = f2bf(sum);
+    }
+  }
+}
+
+// the split-K fold of the bf16 and the fp8 GEMM
+static void launch_reduce_cast(void* out_bf16, const void* part_f32, int M,
+                               int N, int ksplit, void* stream) {
+  long long mn = (long long)M * N;
+  long long blocks = (mn / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(reduce_cast_kernel, dim3((int)blocks), dim3(256), 0,
+                     (hipStream_t)stream, (unsigned short*)out_bf16,
+                     (const float*)part_f32, mn, ksplit);
+}
 
 // ---------------------------------------------------------------------
 // FP8 (OCP e4m3) decode GEMM — the opt-in fp8-weight serving mode.
@@ -1080,46 +1117,35 @@ __global__ __launch_bounds__(256) void skinny_gemm_fp8_kernel(
   }
 }
 
+// one launch of the M class's kernel: out is bf16 [M, N], or f32 slabs
+// when SPLIT
+template <bool SPLIT>
+static void dispatch_skinny_gemm_fp8(void* out, const void* A8,
+                                     const void* a_scale, const void* W8,
+                                     const void* w_scale, int M, int N,
+                                     int K, int ksplit, void* stream) {
+  auto kern = M > 32   ? skinny_gemm_fp8_kernel<SPLIT, 4>
+              : M > 16 ? skinny_gemm_fp8_kernel<SPLIT, 2>
+                       : skinny_gemm_fp8_kernel<SPLIT, 1>;
+  const dim3 grid((N + 31) / 32, ksplit > 1 ? ksplit : 1);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, out,
+                     (const unsigned char*)A8, (const float*)a_scale,
+                     (const unsigned char*)W8, (const float*)w_scale, M, N,
+                     K, ksplit);
+}
+
 void launch_skinny_gemm_fp8(void* out_bf16, void* part_f32, const void* A8,
                             const void* a_scale, const void* W8,
                             const void* w_scale, int M, int N, int K,
                             int ksplit, void* stream) {
-  const int nblocks = (N + 31) / 32;
-  const dim3 grid(nblocks, ksplit > 1 ? ksplit : 1);
-#define FP8_DISPATCH(SPLIT, DEST)                                         \
-  do {                                                                    \
-    if (M > 32)                                                           \
-      hipLaunchKernelGGL((skinny_gemm_fp8_kernel<SPLIT, 4>), grid,        \
-                         dim3(256), 0, (hipStream_t)stream, DEST,         \
-                         (const unsigned char*)A8, (const float*)a_scale, \
-                         (const unsigned char*)W8, (const float*)w_scale, \
-                         M, N, K, ksplit);                                \
-    else if (M > 16)                                                      \
-      hipLaunchKernelGGL((skinny_gemm_fp8_kernel<SPLIT, 2>), grid,        \
-                         dim3(256), 0, (hipStream_t)stream, DEST,         \
-                         (const unsigned char*)A8, (const float*)a_scale, \
-                         (const unsigned char*)W8, (const float*)w_scale, \
-                         M, N, K, ksplit);                                \
-    else                                                                  \
-      hipLaunchKernelGGL((skinny_gemm_fp8_kernel<SPLIT, 1>), grid,        \
-                         dim3(256), 0, (hipStream_t)stream, DEST,         \
-                         (const unsigned char*)A8, (const float*)a_scale, \
-                         (const unsigned char*)W8, (const float*)w_scale, \
-                         M, N, K, ksplit);                                \
-  } while (0)
   if (ksplit <= 1) {
-    FP8_DISPATCH(false, out_bf16);
+    dispatch_skinny_gemm_fp8<false>(out_bf16, A8, a_scale, W8, w_scale, M, N,
+                                    K, ksplit, stream);
   } else {
-    FP8_DISPATCH(true, part_f32);
-    long long mn = (long long)M * N;
-    long long blocks = (mn / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(reduce_cast_kernel, dim3((int)blocks), dim3(256), 0,
-                       (hipStream_t)stream, (unsigned short*)out_bf16,
-                       (const float*)part_f32, mn, ksplit);
+    dispatch_skinny_gemm_fp8<true>(part_f32, A8, a_scale, W8, w_scale, M, N,
+                                   K, ksplit, stream);
+    launch_reduce_cast(out_bf16, part_f32, M, N, ksplit, stream);
   }
-#undef FP8_DISPATCH
 }
 
 // dynamic per-row fp8 quantization of bf16 activations:
@@ -1176,35 +1202,6 @@ void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
                      (float*)a_scale, (const unsigned short*)a, cols);
 }
 
-// fold ksplit partial slabs [ksplit, M, N] f32 -> bf16 [M, N]
-__global__ void reduce_cast_kernel(unsigned short* __restrict__ out,
-                                   const float* __restrict__ part,
-                                   long long mn, int ksplit) {
-  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  long long stride = (long long)gridDim.x * blockDim.x * 4;
-  for (; i + 3 < mn; i += stride) {
-    f32x4v sum = *reinterpret_cast<const f32x4v*>(part + i);
-    for (int s = 1; s < ksplit; ++s) {
-      f32x4v v = *reinterpret_cast<const f32x4v*>(part + (size_t)s * mn + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sum[j] += v[j];
-    }
-    unsigned short o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = f2bf(sum[j]);
-    *reinterpret_cast<uint64_t*>(out + i) =
-        *reinterpret_cast<const uint64_t*>(o);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    for (long long t = (mn & ~3LL); t < mn; ++t) {
-      float sum = part[t];
-      for (int s = 1; s < ksplit; ++s) sum += part[(size_t)s * mn + t];
-      out[t] = f2bf(sum);
-    }
-  }
-}
-
-// emit split-K slabs only (consumer kernel folds them)
 // MT=2 wave-split K-loop unroll depth (4 default; 8 doubles the
 // in-flight bytes per wave at +64 VGPRs) — env knob for e2e A/B.
 static int gemm_unr2_env() {
@@ -1229,21 +1226,6 @@ static int gemm_pipe_env() {
   return v;
 }
 
-template <bool SPLIT>
-static bool launch_pipe_mt2(void* out, const void* A, const void* W,
-                            int M, int N, int K, int ksplit,
-                            const dim3& grid, void* stream) {
-  const int depth = gemm_pipe_env();
-  if (depth < 2) return false;
-  auto kern = depth >= 6 ? (skinny_gemm_ws_pipe_kernel<SPLIT, 2, 6>)
-              : depth >= 4 ? (skinny_gemm_ws_pipe_kernel<SPLIT, 2, 4>)
-                           : (skinny_gemm_ws_pipe_kernel<SPLIT, 2, 3>);
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, out,
-                     (const unsigned short*)A, (const unsigned short*)W,
-                     M, N, K, ksplit);
-  return true;
-}
-
 // MLRUN_GEMM_LDS_RING=64x2|64x3|128x2 selects the (STAGE_K, DEPTH) ring
 // of the variant-4 LDS-DMA kernel: 64, 96 or 128 KiB of LDS per
 // workgroup.  Read once.  Default 64x2: two workgroups fit a CU, and it
@@ -1258,8 +1240,10 @@ static int gemm_lds_ring_env() {
   return v;
 }
 
-typedef void (*lds_ring_kern_t)(void*, const unsigned short*,
-                                const unsigned short*, int, int, int, int);
+// every bf16 skinny GEMM kernel: (out, A, W, M, N, K, ksplit)
+typedef void (*skinny_gemm_kern_t)(void*, const unsigned short*,
+                                   const unsigned short*, int, int, int,
+                                   int);
 
 template <int STAGE_K, int DEPTH>
 constexpr int lds_ring_bytes() {
@@ -1281,7 +1265,7 @@ static void lds_ring_allow_all() {
   if (done[dev].load(std::memory_order_acquire)) return;
   std::lock_guard<std::mutex> lock(mu);
   if (done[dev].load(std::memory_order_relaxed)) return;
-  const struct { lds_ring_kern_t kern; int bytes; } all[] = {
+  const struct { skinny_gemm_kern_t kern; int bytes; } all[] = {
       {skinny_gemm_ws_lds_kernel<false, 64, 2>, lds_ring_bytes<64, 2>()},
       {skinny_gemm_ws_lds_kernel<true, 64, 2>, lds_ring_bytes<64, 2>()},
       {skinny_gemm_ws_lds_kernel<false, 64, 3>, lds_ring_bytes<64, 3>()},
@@ -1296,184 +1280,78 @@ static void lds_ring_allow_all() {
   done[dev].store(true, std::memory_order_release);
 }
 
-template <bool SPLIT, int STAGE_K, int DEPTH>
-static void launch_lds_ring(void* out, const void* A, const void* W, int M,
-                            int N, int K, int ksplit, const dim3& grid,
-                            void* stream) {
-  lds_ring_kern_t kern = skinny_gemm_ws_lds_kernel<SPLIT, STAGE_K, DEPTH>;
-  constexpr int bytes = lds_ring_bytes<STAGE_K, DEPTH>();
-  lds_ring_allow_all();
-  hipLaunchKernelGGL(kern, grid, dim3(256), bytes, (hipStream_t)stream, out,
-                     (const unsigned short*)A, (const unsigned short*)W, M,
-                     N, K, ksplit);
-}
-
-// variant 4, 16 < M <= 32
+// The one dispatch of the bf16 skinny GEMM: pick the kernel of this
+// (variant, M class, env knobs) cell and launch it once on the grid
+// (n-tiles, ksplit).  out is bf16 [M, N], or ksplit f32 slabs when SPLIT.
 template <bool SPLIT>
-static void launch_lds_mt2(void* out, const void* A, const void* W, int M,
-                           int N, int K, int ksplit, const dim3& grid,
-                           void* stream) {
-  switch (gemm_lds_ring_env()) {
-    case 1:
-      launch_lds_ring<SPLIT, 64, 3>(out, A, W, M, N, K, ksplit, grid,
-                                    stream);
-      break;
-    case 2:
-      launch_lds_ring<SPLIT, 128, 2>(out, A, W, M, N, K, ksplit, grid,
-                                     stream);
-      break;
-    default:
-      launch_lds_ring<SPLIT, 64, 2>(out, A, W, M, N, K, ksplit, grid,
-                                    stream);
+static void dispatch_skinny_gemm(void* out, const void* A, const void* W,
+                                 int M, int N, int K, int ksplit,
+                                 int variant, void* stream) {
+  const int nblocks = variant == 3 ? (N + 15) / 16
+                      : variant >= 1 ? (N + 31) / 32 : (N + 127) / 128;
+  const int mt = M > 32 ? 4 : M > 16 ? 2 : 1;  // 16-row M tiles per wave
+  skinny_gemm_kern_t kern;
+  int lds_bytes = 0;
+  if (variant == 4 && mt == 2) {
+    lds_ring_allow_all();
+    switch (gemm_lds_ring_env()) {
+      case 1:
+        kern = skinny_gemm_ws_lds_kernel<SPLIT, 64, 3>;
+        lds_bytes = lds_ring_bytes<64, 3>();
+        break;
+      case 2:
+        kern = skinny_gemm_ws_lds_kernel<SPLIT, 128, 2>;
+        lds_bytes = lds_ring_bytes<128, 2>();
+        break;
+      default:
+        kern = skinny_gemm_ws_lds_kernel<SPLIT, 64, 2>;
+        lds_bytes = lds_ring_bytes<64, 2>();
+    }
+  } else if (variant == 3) {
+    // 16-wide n-tiles: 2x the workgroups at unchanged per-wave K
+    kern = mt == 4   ? skinny_gemm_ws_kernel<SPLIT, 4, 4, 1>
+           : mt == 2 ? skinny_gemm_ws_kernel<SPLIT, 2, 4, 1>
+                     : skinny_gemm_ws_kernel<SPLIT, 1, 4, 1>;
+  } else if (variant >= 1) {
+    const int depth = gemm_pipe_env();
+    if (mt == 4)
+      kern = skinny_gemm_ws_kernel<SPLIT, 4>;
+    else if (mt == 1)
+      kern = skinny_gemm_ws_kernel<SPLIT, 1>;
+    else if (depth >= 2)  // the software-pipelined ring
+      kern = depth >= 6   ? skinny_gemm_ws_pipe_kernel<SPLIT, 2, 6>
+             : depth >= 4 ? skinny_gemm_ws_pipe_kernel<SPLIT, 2, 4>
+                          : skinny_gemm_ws_pipe_kernel<SPLIT, 2, 3>;
+    else
+      kern = gemm_unr2_env() >= 8 ? skinny_gemm_ws_kernel<SPLIT, 2, 8>
+                                  : skinny_gemm_ws_kernel<SPLIT, 2, 4>;
+  } else {
+    kern = mt == 4   ? skinny_gemm_kernel<SPLIT, 4>
+           : mt == 2 ? skinny_gemm_kernel<SPLIT, 2>
+                     : skinny_gemm_kernel<SPLIT, 1>;
   }
+  hipLaunchKernelGGL(kern, dim3(nblocks, ksplit), dim3(256), lds_bytes,
+                     (hipStream_t)stream, out, (const unsigned short*)A,
+                     (const unsigned short*)W, M, N, K, ksplit);
 }
 
+// emit split-K slabs only (a consumer kernel folds them)
 void launch_skinny_gemm_slabs(void* part_f32, const void* A, const void* W,
                               int M, int N, int K, int ksplit, int variant,
                               void* stream) {
-  const int nblocks = variant == 3 ? (N + 15) / 16
-                      : variant >= 1 ? (N + 31) / 32 : (N + 127) / 128;
-  const dim3 grid(nblocks, ksplit);
-  if (variant == 4 && M > 16 && M <= 32) {
-    launch_lds_mt2<true>(part_f32, A, W, M, N, K, ksplit, grid, stream);
-  } else if (variant == 3) {
-    // 16-wide n-tiles: 2x the workgroups at unchanged per-wave K
-    if (M > 32)
-      hipLaunchKernelGGL((skinny_gemm_ws_kernel<true, 4, 4, 1>), grid,
-                         dim3(256), 0, (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-    else if (M > 16)
-      hipLaunchKernelGGL((skinny_gemm_ws_kernel<true, 2, 4, 1>), grid,
-                         dim3(256), 0, (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-    else
-      hipLaunchKernelGGL((skinny_gemm_ws_kernel<true, 1, 4, 1>), grid,
-                         dim3(256), 0, (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-  } else if (variant >= 1) {
-    if (M > 32)
-      hipLaunchKernelGGL((skinny_gemm_ws_kernel<true, 4>), grid, dim3(256),
-                         0, (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-    else if (M > 16) {
-      if (!launch_pipe_mt2<true>(part_f32, A, W, M, N, K, ksplit, grid,
-                                 stream))
-        hipLaunchKernelGGL(gemm_unr2_env() >= 8
-                               ? (skinny_gemm_ws_kernel<true, 2, 8>)
-                               : (skinny_gemm_ws_kernel<true, 2, 4>),
-                           grid, dim3(256),
-                           0, (hipStream_t)stream, part_f32,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, ksplit);
-    }
-    else
-      hipLaunchKernelGGL((skinny_gemm_ws_kernel<true, 1>), grid, dim3(256),
-                         0, (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-  } else {
-    if (M > 32)
-      hipLaunchKernelGGL((skinny_gemm_kernel<true, 4>), grid, dim3(256), 0,
-                         (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-    else if (M > 16)
-      hipLaunchKernelGGL((skinny_gemm_kernel<true, 2>), grid, dim3(256), 0,
-                         (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-    else
-      hipLaunchKernelGGL((skinny_gemm_kernel<true, 1>), grid, dim3(256), 0,
-                         (hipStream_t)stream, part_f32,
-                         (const unsigned short*)A, (const unsigned short*)W,
-                         M, N, K, ksplit);
-  }
+  dispatch_skinny_gemm<true>(part_f32, A, W, M, N, K, ksplit, variant,
+                             stream);
 }
 
 void launch_skinny_gemm(void* out_bf16, void* part_f32, const void* A,
                         const void* W, int M, int N, int K, int ksplit,
                         int variant, void* stream) {
-  if (ksplit < 1) ksplit = 1;
-  const int nblocks = variant == 3 ? (N + 15) / 16
-                      : variant >= 1 ? (N + 31) / 32 : (N + 127) / 128;
-  if (ksplit == 1) {
-    if (variant == 4 && M > 16 && M <= 32) {
-      launch_lds_mt2<false>(out_bf16, A, W, M, N, K, 1, dim3(nblocks),
-                            stream);
-    } else if (variant == 3) {
-      if (M > 32)
-        hipLaunchKernelGGL((skinny_gemm_ws_kernel<false, 4, 4, 1>),
-                           dim3(nblocks), dim3(256), 0,
-                           (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-      else if (M > 16)
-        hipLaunchKernelGGL((skinny_gemm_ws_kernel<false, 2, 4, 1>),
-                           dim3(nblocks), dim3(256), 0,
-                           (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-      else
-        hipLaunchKernelGGL((skinny_gemm_ws_kernel<false, 1, 4, 1>),
-                           dim3(nblocks), dim3(256), 0,
-                           (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-    } else if (variant >= 1) {
-      if (M > 32)
-        hipLaunchKernelGGL((skinny_gemm_ws_kernel<false, 4>),
-                           dim3(nblocks), dim3(256), 0,
-                           (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-      else if (M > 16) {
-        if (!launch_pipe_mt2<false>(out_bf16, A, W, M, N, K, 1,
-                                    dim3(nblocks), stream))
-          hipLaunchKernelGGL(gemm_unr2_env() >= 8
-                                 ? (skinny_gemm_ws_kernel<false, 2, 8>)
-                                 : (skinny_gemm_ws_kernel<false, 2, 4>),
-                             dim3(nblocks), dim3(256), 0,
-                             (hipStream_t)stream, out_bf16,
-                             (const unsigned short*)A,
-                             (const unsigned short*)W, M, N, K, 1);
-      }
-      else
-        hipLaunchKernelGGL((skinny_gemm_ws_kernel<false, 1>),
-                           dim3(nblocks), dim3(256), 0,
-                           (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-    } else {
-      if (M > 32)
-        hipLaunchKernelGGL((skinny_gemm_kernel<false, 4>), dim3(nblocks),
-                           dim3(256), 0, (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-      else if (M > 16)
-        hipLaunchKernelGGL((skinny_gemm_kernel<false, 2>), dim3(nblocks),
-                           dim3(256), 0, (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-      else
-        hipLaunchKernelGGL((skinny_gemm_kernel<false, 1>), dim3(nblocks),
-                           dim3(256), 0, (hipStream_t)stream, out_bf16,
-                           (const unsigned short*)A,
-                           (const unsigned short*)W, M, N, K, 1);
-    }
+  if (ksplit <= 1) {
+    dispatch_skinny_gemm<false>(out_bf16, A, W, M, N, K, 1, variant, stream);
   } else {
-    launch_skinny_gemm_slabs(part_f32, A, W, M, N, K, ksplit, variant,
-                             stream);
-    long long mn = (long long)M * N;
-    long long blocks = (mn / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(reduce_cast_kernel, dim3((int)blocks), dim3(256), 0,
-                       (hipStream_t)stream, (unsigned short*)out_bf16,
-                       (const float*)part_f32, mn, ksplit);
+    dispatch_skinny_gemm<true>(part_f32, A, W, M, N, K, ksplit, variant,
+                               stream);
+    launch_reduce_cast(out_bf16, part_f32, M, N, ksplit, stream);
   }
 }
 
@@ -2269,6 +2147,146 @@ DEV short pf_f2bf(float f) {
   return __builtin_bit_cast(short, (__bf16)f);
 }
 
+// ---- the tile pipeline shared by attn_prefill and attn_verify --------
+
+// Q fragments of one lane: loaded once, live across the whole tile loop
+DEV void pf_load_q(short8v (&qf)[4], const unsigned short* qp) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+    qf[ks] = *reinterpret_cast<const short8v*>(qp + ks * 32);
+}
+
+// K/V staging of one thread: a 64-row tile is 64 x 16 chunks of 16 B,
+// 4 chunks of K and 4 of V per thread, held in registers between the
+// global load (issue) and the LDS write (commit)
+struct PfStage {
+  const unsigned short* kbase;  // cache rows of this (slot, kv head)
+  const unsigned short* vbase;
+  unsigned short* kbuf;
+  unsigned short* vbuf;
+  int kv_end;  // rows at or past it are staged as zeros
+  int tid;
+  short8v kreg[4], vreg[4];
+
+  DEV void issue(int tile0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      const int key = tile0 + (c >> 4);
+      const short8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
+      kreg[i] = zero;
+      vreg[i] = zero;
+      if (key < kv_end) {
+        const size_t off = (size_t)key * 128 + (c & 15) * 8;
+        kreg[i] = *reinterpret_cast<const short8v*>(kbase + off);
+        vreg[i] = *reinterpret_cast<const short8v*>(vbase + off);
+      }
+    }
+  }
+  DEV void commit() const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = tid + 256 * i;
+      const int off = (c >> 4) * PF_ROW + (c & 15) * 8;
+      *reinterpret_cast<short8v*>(kbuf + off) = kreg[i];
+      *reinterpret_cast<short8v*>(vbuf + off) = vreg[i];
+    }
+  }
+};
+
+// One 64-key tile for one wave's 16 columns: both products and the
+// online softmax between them.  `pos` is the lane's query position;
+// need_mask (wave-uniform) says whether the tile reaches past the
+// lowest position of the wave, so that keys > pos must be masked.
+DEV void pf_tile(const unsigned short* kbuf, const unsigned short* vbuf,
+                 const short8v (&qf)[4], f32x4v (&o)[8], float& m, float& l,
+                 int tile0, bool need_mask, int pos, float scale_log2e,
+                 int lq, int lh) {
+  // --- S^T = K . Q^T : 4 key tiles x 4 k-steps
+  f32x4v s[4];
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+    s[kt] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    const unsigned short* kp = kbuf + (kt * 16 + lq) * PF_ROW + lh * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const short8v kf = *reinterpret_cast<const short8v*>(kp + ks * 32);
+      s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[kt], 0,
+                                                      0, 0);
+    }
+  }
+  // --- scale, causal mask, tile max
+  float mx = -__builtin_inff();
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float x = s[kt][r] * scale_log2e;
+      if (need_mask && tile0 + kt * 16 + lh * 4 + r > pos)
+        x = -__builtin_inff();
+      s[kt][r] = x;
+      mx = fmaxf(mx, x);
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  // --- online softmax: rescale everything held at the old max.  A
+  // column with no visible key in this tile has mx = -inf: m stays put,
+  // alpha = 1 and every p = exp2(-inf) = 0
+  const float m_new = fmaxf(m, mx);
+  const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+  m = m_new;
+  float psum = 0.f;
+  short8v pb[2];
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_new);
+      psum += p;
+      pb[kt >> 1][(kt & 1) * 4 + r] = pf_f2bf(p);
+    }
+  }
+  l = l * alpha + psum;
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
+  // --- O^T += V^T . P^T : 8 dim tiles x 2 k-steps of 32 keys
+  const unsigned short* vp =
+      vbuf + (lh * 4 + (lq >> 2)) * PF_ROW + (lq & 3) * 4;
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const short4v lo = pf_read_tr16(vp + (ks * 32) * PF_ROW + dt * 16);
+      const short4v hi =
+          pf_read_tr16(vp + (ks * 32 + 16) * PF_ROW + dt * 16);
+      const short8v vf =
+          __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks], o[dt], 0,
+                                                      0, 0);
+    }
+  }
+}
+
+// finish a column's sum across the 4 lanes that share it
+DEV float pf_finish_l(float l) {
+  l += __shfl_xor(l, 16, 64);
+  return l + __shfl_xor(l, 32, 64);
+}
+
+// normalised bf16 output of one lane: 4 dims of each of the 8 dim tiles
+DEV void pf_store_bf16(unsigned short* op, const f32x4v (&o)[8], float inv) {
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) {
+    ushort4 w;
+    w.x = f2bf(o[dt][0] * inv);
+    w.y = f2bf(o[dt][1] * inv);
+    w.z = f2bf(o[dt][2] * inv);
+    w.w = f2bf(o[dt][3] * inv);
+    *reinterpret_cast<ushort4*>(op + dt * 16) = w;
+  }
+}
+
 __global__ __launch_bounds__(256) void attn_prefill_kernel(
     unsigned short* __restrict__ O, const unsigned short* __restrict__ Q,
     const unsigned short* __restrict__ Kc,
@@ -2311,48 +2329,13 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
   const int wave_min_pos = start + wrow0;
   const int wave_max_pos = start + min(wrow0 + 15, qlen - 1);
 
-  // --- Q fragments: loaded once, live across the whole tile loop
   short8v qf[4];
-  {
-    const unsigned short* qp =
-        Q + (size_t)(row0 + min(qr, qlen - 1)) * q_row_stride +
-        (size_t)h * D + lh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      qf[ks] = *reinterpret_cast<const short8v*>(qp + ks * 32);
-  }
+  pf_load_q(qf, Q + (size_t)(row0 + min(qr, qlen - 1)) * q_row_stride +
+                    (size_t)h * D + lh * 8);
 
   const int kvh = h / (Hq / Hkv);
   const size_t cbase = ((size_t)slot * Hkv + kvh) * Smax * D;
-  const unsigned short* kbase = Kc + cbase;
-  const unsigned short* vbase = Vc + cbase;
-
-  // staging: 64 rows x 16 chunks of 16 B = 4 chunks per thread
-  short8v kreg[4], vreg[4];
-  auto issue = [&](int tile0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 256 * i;
-      const int key = tile0 + (c >> 4);
-      const short8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
-      kreg[i] = zero;
-      vreg[i] = zero;
-      if (key < kv_end) {
-        const size_t off = (size_t)key * D + (c & 15) * 8;
-        kreg[i] = *reinterpret_cast<const short8v*>(kbase + off);
-        vreg[i] = *reinterpret_cast<const short8v*>(vbase + off);
-      }
-    }
-  };
-  auto commit = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 256 * i;
-      const int off = (c >> 4) * PF_ROW + (c & 15) * 8;
-      *reinterpret_cast<short8v*>(kbuf + off) = kreg[i];
-      *reinterpret_cast<short8v*>(vbuf + off) = vreg[i];
-    }
-  };
+  PfStage st{Kc + cbase, Vc + cbase, kbuf, vbuf, kv_end, tid};
 
   f32x4v o[8];
 #pragma unroll
@@ -2360,96 +2343,25 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(
   float m = -1e30f;  // running row max (log2 domain), finite on purpose
   float l = 0.f;     // this lane's share of the row sum
 
-  issue(0);
+  st.issue(0);
   for (int t = 0; t < ntiles; ++t) {
     const int tile0 = t * PF_BN;
     __syncthreads();  // everyone is done reading the previous tile
-    commit();
+    st.commit();
     __syncthreads();
-    if (t + 1 < ntiles) issue(tile0 + PF_BN);  // flies under the MFMAs
+    if (t + 1 < ntiles) st.issue(tile0 + PF_BN);  // flies under the MFMAs
     if (!wave_active || tile0 > wave_max_pos) continue;
-
-    // --- S^T = K . Q^T : 4 key tiles x 4 k-steps
-    f32x4v s[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      s[kt] = f32x4v{0.f, 0.f, 0.f, 0.f};
-      const unsigned short* kp = kbuf + (kt * 16 + lq) * PF_ROW + lh * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const short8v kf = *reinterpret_cast<const short8v*>(kp + ks * 32);
-        s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[kt],
-                                                        0, 0, 0);
-      }
-    }
-    // --- scale, causal mask on diagonal tiles only, tile max
+    // causal mask on diagonal tiles only
     const bool need_mask = tile0 + PF_BN - 1 > wave_min_pos;
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float x = s[kt][r] * scale_log2e;
-        if (need_mask && tile0 + kt * 16 + lh * 4 + r > pos)
-          x = -__builtin_inff();
-        s[kt][r] = x;
-        mx = fmaxf(mx, x);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // --- online softmax: rescale everything held at the old max
-    const float m_new = fmaxf(m, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-    m = m_new;
-    float psum = 0.f;
-    short8v pb[2];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_new);
-        psum += p;
-        pb[kt >> 1][(kt & 1) * 4 + r] = pf_f2bf(p);
-      }
-    }
-    l = l * alpha + psum;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
-    // --- O^T += V^T . P^T : 8 dim tiles x 2 k-steps of 32 keys
-    const unsigned short* vp =
-        vbuf + (lh * 4 + (lq >> 2)) * PF_ROW + (lq & 3) * 4;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const short4v lo = pf_read_tr16(vp + (ks * 32) * PF_ROW + dt * 16);
-        const short4v hi =
-            pf_read_tr16(vp + (ks * 32 + 16) * PF_ROW + dt * 16);
-        const short8v vf =
-            __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks], o[dt],
-                                                        0, 0, 0);
-      }
-    }
+    pf_tile(kbuf, vbuf, qf, o, m, l, tile0, need_mask, pos, scale_log2e, lq,
+            lh);
   }
 
-  // --- epilogue: finish the row sum across the 4 lanes of a row
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
+  // --- epilogue
+  l = pf_finish_l(l);
   if (!row_valid) return;
-  const float inv = 1.f / l;
-  unsigned short* op =
-      O + ((size_t)(row0 + qr) * Hq + h) * D + lh * 4;
-#pragma unroll
-  for (int dt = 0; dt < 8; ++dt) {
-    ushort4 w;
-    w.x = f2bf(o[dt][0] * inv);
-    w.y = f2bf(o[dt][1] * inv);
-    w.z = f2bf(o[dt][2] * inv);
-    w.w = f2bf(o[dt][3] * inv);
-    *reinterpret_cast<ushort4*>(op + dt * 16) = w;
-  }
+  pf_store_bf16(O + ((size_t)(row0 + qr) * Hq + h) * D + lh * 4, o,
+                1.f / l);
 }
 
 void launch_attn_prefill(void* O, const void* Q, const void* Kc,
@@ -2483,8 +2395,9 @@ void launch_attn_prefill(void* O, const void* Q, const void* Kc,
 // (column c = g * QL + j, <= 64 of them, 16 per wave), so K/V are read
 // from HBM once per KV head instead of once per q-head, and a column
 // tile is as full as G x QL allows (G=4, QL=4: exactly 16).  The two
-// products, the register-resident P, the transposed V read and the
-// staging (zeros at and past base + QL) are attn_prefill's.  Waves
+// products, the register-resident P and the transposed V read (pf_tile)
+// and the staging (PfStage, zeros at and past base + QL) are the code
+// attn_prefill runs.  Waves
 // whose column tile is empty only help with staging: the kernel is
 // bound by the K/V stream, not by the MFMAs of its one or two busy
 // waves (32 MFMAs per 32 KB tile).
@@ -2548,46 +2461,11 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(
   const int pos = base + j;  // this lane's query position
   const size_t qrow = (size_t)b * QL + j;
 
-  // --- Q fragments: loaded once, live across the whole tile loop
   short8v qf[4];
-  {
-    const unsigned short* qp =
-        Q + qrow * q_row_stride + (size_t)h * D + lh * 8;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      qf[ks] = *reinterpret_cast<const short8v*>(qp + ks * 32);
-  }
+  pf_load_q(qf, Q + qrow * q_row_stride + (size_t)h * D + lh * 8);
 
   const size_t cbase = ((size_t)b * Hkv + kvh) * Smax * D;
-  const unsigned short* kbase = Kc + cbase;
-  const unsigned short* vbase = Vc + cbase;
-
-  // staging: 64 rows x 16 chunks of 16 B = 4 chunks per thread
-  short8v kreg[4], vreg[4];
-  auto issue = [&](int tile0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 256 * i;
-      const int key = tile0 + (c >> 4);
-      const short8v zero = {0, 0, 0, 0, 0, 0, 0, 0};
-      kreg[i] = zero;
-      vreg[i] = zero;
-      if (key < kv_end) {
-        const size_t off = (size_t)key * D + (c & 15) * 8;
-        kreg[i] = *reinterpret_cast<const short8v*>(kbase + off);
-        vreg[i] = *reinterpret_cast<const short8v*>(vbase + off);
-      }
-    }
-  };
-  auto commit = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = tid + 256 * i;
-      const int off = (c >> 4) * PF_ROW + (c & 15) * 8;
-      *reinterpret_cast<short8v*>(kbuf + off) = kreg[i];
-      *reinterpret_cast<short8v*>(vbuf + off) = vreg[i];
-    }
-  };
+  PfStage st{Kc + cbase, Vc + cbase, kbuf, vbuf, kv_end, tid};
 
   f32x4v o[8];
 #pragma unroll
@@ -2595,98 +2473,26 @@ __global__ __launch_bounds__(256) void attn_verify_kernel(
   float m = -1e30f;  // running column max (log2 domain), finite on purpose
   float l = 0.f;     // this lane's share of the column sum
 
-  issue(t_begin * PF_BN);
+  st.issue(t_begin * PF_BN);
   for (int t = t_begin; t < t_end; ++t) {
     const int tile0 = t * PF_BN;
     __syncthreads();  // everyone is done reading the previous tile
-    commit();
+    st.commit();
     __syncthreads();
-    if (t + 1 < t_end) issue(tile0 + PF_BN);  // flies under the MFMAs
+    if (t + 1 < t_end) st.issue(tile0 + PF_BN);  // flies under the MFMAs
     if (!wave_active) continue;
-
-    // --- S^T = K . Q^T : 4 key tiles x 4 k-steps
-    f32x4v s[4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      s[kt] = f32x4v{0.f, 0.f, 0.f, 0.f};
-      const unsigned short* kp = kbuf + (kt * 16 + lq) * PF_ROW + lh * 8;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const short8v kf = *reinterpret_cast<const short8v*>(kp + ks * 32);
-        s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], s[kt],
-                                                        0, 0, 0);
-      }
-    }
-    // --- scale, per-column causal mask on the tiles past `base`, max
+    // per-column causal mask on the tiles past `base`
     const bool need_mask = tile0 + PF_BN - 1 > base;
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float x = s[kt][r] * scale_log2e;
-        if (need_mask && tile0 + kt * 16 + lh * 4 + r > pos)
-          x = -__builtin_inff();
-        s[kt][r] = x;
-        mx = fmaxf(mx, x);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // --- online softmax; a column with no visible key in this tile has
-    // mx = -inf: m stays put, alpha = 1 and every p = exp2(-inf) = 0
-    const float m_new = fmaxf(m, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-    m = m_new;
-    float psum = 0.f;
-    short8v pb[2];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_new);
-        psum += p;
-        pb[kt >> 1][(kt & 1) * 4 + r] = pf_f2bf(p);
-      }
-    }
-    l = l * alpha + psum;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
-    // --- O^T += V^T . P^T : 8 dim tiles x 2 k-steps of 32 keys
-    const unsigned short* vp =
-        vbuf + (lh * 4 + (lq >> 2)) * PF_ROW + (lq & 3) * 4;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const short4v lo = pf_read_tr16(vp + (ks * 32) * PF_ROW + dt * 16);
-        const short4v hi =
-            pf_read_tr16(vp + (ks * 32 + 16) * PF_ROW + dt * 16);
-        const short8v vf =
-            __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[ks], o[dt],
-                                                        0, 0, 0);
-      }
-    }
+    pf_tile(kbuf, vbuf, qf, o, m, l, tile0, need_mask, pos, scale_log2e, lq,
+            lh);
   }
 
-  // --- epilogue: finish the column sum across its 4 lanes
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
+  // --- epilogue
+  l = pf_finish_l(l);
   if (!col_valid) return;
   const size_t orow = qrow * Hq + h;
   if (!SPLIT) {
-    const float inv = (l > 0.f) ? 1.f / l : 0.f;
-    unsigned short* op = O + orow * D + lh * 4;
-#pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
-      ushort4 w;
-      w.x = f2bf(o[dt][0] * inv);
-      w.y = f2bf(o[dt][1] * inv);
-      w.z = f2bf(o[dt][2] * inv);
-      w.w = f2bf(o[dt][3] * inv);
-      *reinterpret_cast<ushort4*>(op + dt * 16) = w;
-    }
+    pf_store_bf16(O + orow * D + lh * 4, o, (l > 0.f) ? 1.f / l : 0.f);
   } else {
     float* prow = ws + (orow * nsplit + split) * VF_WS_ROW;
 #pragma unroll
