@@ -158,13 +158,61 @@ LORA_PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
 class SamplingParams:
     """How one prompt's tokens are chosen under ``sampling="request"``:
     the defaults are greedy with every filter off.  ``logprobs`` asks
-    the server to return the chosen tokens' log-probabilities."""
+    the server to return the chosen tokens' log-probabilities.
+
+    The last four fields change the distribution a row samples from and
+    need an engine built with ``logit_processors=True``; their defaults
+    are neutral.  ``repetition_penalty`` r in [0.1, 10] divides the
+    positive and multiplies the other logits of every token the prompt
+    or the output holds; ``frequency_penalty`` f and ``presence_penalty``
+    p in [-2, 2] subtract ``f * n + p`` from a token generated n > 0
+    times; ``logit_bias`` maps at most 64 token ids (ints or decimal
+    strings) to an addend in [-100, 100].  Applied in that order."""
     temperature: float = 0.0
     top_k: int = 0
     top_p: float = 1.0
     min_p: float = 0.0
     seed: int = 0
     logprobs: bool = False
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: typing.Optional[dict] = None
+
+    def bias_items(self):
+        """logit_bias as [(token id, value)] with int ids; ValueError
+        naming the field."""
+        if self.logit_bias is None:
+            return []
+        if not isinstance(self.logit_bias, dict):
+            raise ValueError("logit_bias must map token ids to numbers, "
+                             f"got {self.logit_bias!r}")
+        if len(self.logit_bias) > ops.LOGIT_BIAS_MAX:
+            raise ValueError(f"logit_bias holds {len(self.logit_bias)} "
+                             f"entries, at most {ops.LOGIT_BIAS_MAX}")
+        items = {}
+        for key, value in self.logit_bias.items():
+            if isinstance(key, str) and key.isascii() and key.isdigit():
+                key = int(key)
+            if isinstance(key, bool) or not isinstance(key, int) or key < 0:
+                raise ValueError("logit_bias keys must be token ids >= 0 "
+                                 f"(ints or decimal strings), got {key!r}")
+            if key in items:
+                raise ValueError(f"logit_bias names token {key} twice")
+            if isinstance(value, bool) or \
+                    not isinstance(value, (int, float)) or \
+                    not -100 <= value <= 100:
+                raise ValueError("logit_bias values must be numbers in "
+                                 f"[-100, 100], got {value!r} for token "
+                                 f"{key}")
+            items[key] = float(value)
+        return list(items.items())
+
+    def neutral_processors(self) -> bool:
+        """Whether the four logit-processor fields leave logits alone."""
+        return self.repetition_penalty == 1 and \
+            self.presence_penalty == 0 and self.frequency_penalty == 0 \
+            and not self.logit_bias
 
     def validate(self):
         """ValueError naming the field that is out of range."""
@@ -200,6 +248,16 @@ class SamplingParams:
         if not isinstance(self.logprobs, bool):
             raise ValueError(f"logprobs must be true or false, got "
                              f"{self.logprobs!r}")
+        number("repetition_penalty", self.repetition_penalty)
+        if not 0.1 <= self.repetition_penalty <= 10:
+            raise ValueError("repetition_penalty must be in [0.1, 10], "
+                             f"got {self.repetition_penalty}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            number(name, getattr(self, name))
+            if not -2 <= getattr(self, name) <= 2:
+                raise ValueError(f"{name} must be in [-2, 2], got "
+                                 f"{getattr(self, name)}")
+        self.bias_items()
         return self
 
 
@@ -313,10 +371,16 @@ class LlamaDecodeEngine:
                  weight_dtype: str = "bf16", kv_dtype: str = "bf16",
                  temperature: float = 0.0, top_k: int = 0,
                  max_adapters: int = 0, lora_rank: int = 16,
-                 lora: "LoraTables" = None, sampling: str = "engine"):
+                 lora: "LoraTables" = None, sampling: str = "engine",
+                 logit_processors: bool = False):
         if sampling not in ("engine", "request"):
             raise ValueError(f"unknown sampling mode {sampling!r} "
                              "(expected 'engine' or 'request')")
+        if logit_processors and sampling != "request":
+            raise ValueError(
+                f"logit_processors=True needs sampling=\"request\", got "
+                f"sampling={sampling!r}: penalties and logit bias are "
+                "per-request parameters")
         if sampling == "request" and tp_size > 1:
             raise ValueError(
                 f'sampling="request" conflicts with tp_size={tp_size}: '
@@ -479,18 +543,43 @@ class LlamaDecodeEngine:
             self.buf_logprob = torch.zeros(B, dtype=torch.float32,
                                            device=dev)
             self.buf_kept = torch.zeros(B, dtype=torch.int32, device=dev)
+        # logit processors (opt-in, on top of sampling="request"): per
+        # slot the penalties, the bias entries and the token-state row
+        # (2 * times generated + in prompt) that ops.logit_processors
+        # reads and maintains between the lm_head GEMM and the sampler.
+        # All neutral: such a row costs a workgroup exit.  With the flag
+        # off nothing is allocated and the step launches what it did.
+        self.logit_processors = bool(logit_processors)
+        if self.logit_processors:
+            dev, NB = self.device, ops.LOGIT_BIAS_MAX
+            self.buf_tok_state = torch.zeros(B, cfg.vocab_size,
+                                             dtype=torch.int32, device=dev)
+            self.buf_penalties = torch.tensor(
+                [[1.0, 0.0, 0.0]] * B, dtype=torch.float32).to(dev)
+            self.buf_bias_ids = torch.zeros(B, NB, dtype=torch.int32,
+                                            device=dev)
+            self.buf_bias_val = torch.zeros(B, NB, dtype=torch.float32,
+                                            device=dev)
+            self.buf_bias_n = torch.zeros(B, dtype=torch.int32, device=dev)
         # speculative decoding (opt-in): running acceptance counters
         self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
 
     # -------------------------------------------------------- sampling
     def set_sampling(self, slot: int, temperature: float = 0.0,
                      top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0,
-                     seed: int = 0):
+                     seed: int = 0, repetition_penalty: float = 1.0,
+                     presence_penalty: float = 0.0,
+                     frequency_penalty: float = 0.0,
+                     logit_bias: dict = None):
         """Write one slot's sampling parameters (sampling="request"
         engines).  The captured graph reads them on the device, so the
-        change holds from the next step on without a recapture."""
+        change holds from the next step on without a recapture.  The
+        last four need ``logit_processors=True``; a slot counts its
+        generated tokens only while its parameters are not neutral."""
         self.set_sampling_slots([slot], [SamplingParams(
-            temperature, top_k, top_p, min_p, seed)])
+            temperature, top_k, top_p, min_p, seed, False,
+            repetition_penalty, presence_penalty, frequency_penalty,
+            logit_bias)])
 
     def set_sampling_slots(self, slots, params):
         """set_sampling for several slots at once: ``params`` holds one
@@ -512,9 +601,26 @@ class LlamaDecodeEngine:
                 raise ValueError(f"slot {slot} outside [0, {self.B})")
         for item in params:
             item.validate()
+            self._check_processors(item)
         if not slots:
             return
         index = torch.tensor(slots, dtype=torch.long).to(self.device)
+        if self.logit_processors:
+            NB = ops.LOGIT_BIAS_MAX
+            biases = [item.bias_items() for item in params]
+            self.buf_penalties[index] = torch.tensor(
+                [[item.repetition_penalty, item.presence_penalty,
+                  item.frequency_penalty] for item in params],
+                dtype=torch.float32).to(self.device)
+            self.buf_bias_ids[index] = torch.tensor(
+                [[key for key, _ in bias] + [0] * (NB - len(bias))
+                 for bias in biases], dtype=torch.int32).to(self.device)
+            self.buf_bias_val[index] = torch.tensor(
+                [[value for _, value in bias] + [0.0] * (NB - len(bias))
+                 for bias in biases], dtype=torch.float32).to(self.device)
+            self.buf_bias_n[index] = torch.tensor(
+                [len(bias) for bias in biases],
+                dtype=torch.int32).to(self.device)
         for buf, name in ((self.buf_temp_r, "temperature"),
                           (self.buf_top_k, "top_k"),
                           (self.buf_top_p, "top_p"),
@@ -528,6 +634,40 @@ class LlamaDecodeEngine:
             values = torch.tensor(values, dtype=buf.dtype)
             buf[index] = values.to(self.device)
 
+    def _check_processors(self, item: SamplingParams):
+        """ValueError naming the logit-processor field that this engine
+        cannot serve: any non-neutral one without the flag, a bias id
+        outside the vocabulary with it."""
+        if not self.logit_processors:
+            for name, neutral in (("repetition_penalty", 1),
+                                  ("presence_penalty", 0),
+                                  ("frequency_penalty", 0)):
+                if getattr(item, name) != neutral:
+                    raise ValueError(
+                        f"{name}={getattr(item, name)} needs an engine "
+                        "built with logit_processors=True")
+            if item.logit_bias:
+                raise ValueError("logit_bias needs an engine built with "
+                                 "logit_processors=True")
+            return
+        for key, _ in item.bias_items():
+            if key >= self.cfg.vocab_size:
+                raise ValueError(
+                    f"logit_bias names token {key}, outside the "
+                    f"vocabulary [0, {self.cfg.vocab_size})")
+
+    def _prepare_tok_state(self, slots, tok_slot, tokens, fresh=None):
+        """Before a first token is sampled: zero the state rows of the
+        freshly prefilled ``slots`` (a long tensor; ``fresh`` masks
+        those that start a sequence, None = all) and set the in-prompt
+        bit of ``tokens`` [T] in rows ``tok_slot`` [T].  A prefix
+        continuation is not fresh: it ORs its tokens into the row."""
+        state = self.buf_tok_state
+        tok_slot, tokens = tok_slot.long(), tokens.long()
+        state[slots if fresh is None else slots[fresh]] = 0
+        # duplicates write one value: every pair reads the same word
+        state[tok_slot, tokens] = state[tok_slot, tokens] | 1
+
     def _packed_prefill_serves(self) -> bool:
         """Whether prefill_packed (ops.attn_prefill) handles this
         engine: bf16 KV, head_dim 128, group size <= 8."""
@@ -535,12 +675,27 @@ class LlamaDecodeEngine:
         return self.kv_dtype == "bf16" and self.cfg.head_dim == 128 \
             and w.hq % w.hkv == 0 and w.hq // w.hkv <= 8
 
-    def _sample_slots(self, logits, slots):
+    def _sample_slots(self, logits, slots, prompt):
         """First token of freshly prefilled ``slots`` (a long tensor or
         a slice of rows) from their last-token logits [n, vocab], by
-        each slot's own parameters; pos = the prompt length."""
+        each slot's own parameters; pos = the prompt length.  ``prompt``
+        is (tok_slot [T], tokens [T], fresh [n] bool or None): the
+        prompts' tokens with the slot of each, for the token-state rows
+        of a logit_processors engine, whose penalties and bias are
+        applied to the logits, in place, before the draw."""
         logits = logits.contiguous()
         n = logits.shape[0]
+        if self.logit_processors:
+            if isinstance(slots, slice):
+                slots = torch.arange(self.B, device=self.device)[slots]
+            self._prepare_tok_state(slots, *prompt)
+            ops.logit_processors(
+                logits, self.buf_tok_state,
+                self.buf_penalties[slots].contiguous(),
+                self.buf_bias_ids[slots].contiguous(),
+                self.buf_bias_val[slots].contiguous(),
+                self.buf_bias_n[slots].contiguous(),
+                tokens=None, rows=slots.to(torch.int32))
         tokens = torch.empty(n, dtype=torch.int64, device=self.device)
         logprob = torch.empty(n, dtype=torch.float32, device=self.device)
         kept = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -808,6 +963,13 @@ class LlamaDecodeEngine:
         self._gemm(self.buf_hidden, w.lm_head, self.buf_logits,
                    a8=h8, a_scale=h8s)
         if self.sampling == "request":
+            if self.logit_processors:
+                # buf_tokens still holds the token this step consumed:
+                # the newest generated one, the only one not yet counted
+                ops.logit_processors(
+                    self.buf_logits, self.buf_tok_state, self.buf_penalties,
+                    self.buf_bias_ids, self.buf_bias_val, self.buf_bias_n,
+                    tokens=self.buf_tokens)
             # pos = the bumped length: the position of the new token
             ops.sample_tokens(self.buf_logits, self.cache_lens,
                               self.buf_temp_r, self.buf_top_k,
@@ -878,6 +1040,10 @@ class LlamaDecodeEngine:
         sample_backup = [(buf, buf.clone()) for buf in (
             self.buf_logprob, self.buf_kept)] \
             if self.sampling == "request" else []
+        if self.logit_processors:
+            # ... and count their tokens: the table must come back exactly
+            sample_backup.append((self.buf_tok_state,
+                                  self.buf_tok_state.clone()))
         if self.tp_size > 1 and dist.is_available() and \
                 dist.is_initialized():
             # warmup runs REAL collectives — align ranks first so the
@@ -1027,11 +1193,12 @@ class LlamaDecodeEngine:
             return attn.transpose(1, 2).reshape(B * S, w.hq * d)
         return attend
 
-    def _first_tokens(self, logits, slots):
+    def _first_tokens(self, logits, slots, prompt):
         """First token of the freshly prefilled ``slots`` (a long
-        tensor) into buf_tokens, from their last-token logits."""
+        tensor) into buf_tokens, from their last-token logits;
+        ``prompt`` as in _sample_slots."""
         if self.sampling == "request":
-            self._sample_slots(logits, slots)
+            self._sample_slots(logits, slots, prompt)
         elif self.per_slot_temp:
             scores = logits.float() / self.buf_temp[slots]
             u = torch.rand_like(scores).clamp_(1e-9, 1.0 - 1e-9)
@@ -1061,7 +1228,9 @@ class LlamaDecodeEngine:
         last = hidden.view(B, S, -1)[:, -1]
         logits = last @ w.lm_head.t()
         if self.sampling == "request":
-            self._sample_slots(logits, slice(0, B))
+            rows = torch.arange(B, device=self.device)
+            self._sample_slots(logits, slice(0, B), (
+                rows.repeat_interleave(S), tokens.reshape(-1), None))
         return logits
 
     @torch.no_grad()
@@ -1107,7 +1276,8 @@ class LlamaDecodeEngine:
         self.cache_lens[slots] = S
         last = hidden.view(Bp, S, -1)[:, -1]
         logits = last @ w.lm_head.t()
-        self._first_tokens(logits, slots)
+        self._first_tokens(logits, slots, (
+            slots.repeat_interleave(S), tokens.reshape(-1), None))
         return logits
 
     @torch.no_grad()
@@ -1193,7 +1363,8 @@ class LlamaDecodeEngine:
             cu_seqlens[1:] - cu_seqlens[:-1])
         last = hidden[cu_seqlens[1:].long() - 1]
         logits = last @ w.lm_head.t()
-        self._first_tokens(logits, slots_long)
+        self._first_tokens(logits, slots_long, (
+            tok_slot.long(), tokens, kv_start == 0))
         return logits
 
     # -------------------------------------------------------- generate
@@ -1471,6 +1642,13 @@ class LlamaServer:
       with ``seed + j``; a request without a seed gets a random one.
       A request's tokens depend on its prompt, seed and parameters
       only.  Not with ``speculative > 0``.
+    - ``logit_processors``: True (needs ``sampling="request"``) also
+      reads a request's ``repetition_penalty`` ([0.1, 10]),
+      ``presence_penalty`` / ``frequency_penalty`` ([-2, 2]) and
+      ``logit_bias`` ({token id: value in [-100, 100]}, at most 64) and
+      applies them, in that order, with ``ops.logit_processors`` before
+      every draw; logprobs are then those of the processed logits.
+      Without the flag the four fields are not read.
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -1482,7 +1660,8 @@ class LlamaServer:
                  prefill: str = "exact", speculative: int = 0,
                  adapters: dict = None, max_adapters: int = None,
                  lora_rank: int = 16, sampling: str = "engine",
-                 top_p: float = 1.0, min_p: float = 0.0, **class_args):
+                 top_p: float = 1.0, min_p: float = 0.0,
+                 logit_processors: bool = False, **class_args):
         import queue as queue_mod
         import threading
 
@@ -1536,6 +1715,11 @@ class LlamaServer:
             raise ValueError(f"unknown sampling mode {sampling!r} "
                              "(expected 'engine' or 'request')")
         self.sampling = sampling
+        self.logit_processors = bool(logit_processors)
+        if self.logit_processors and sampling != "request":
+            raise ValueError(
+                f"logit_processors=True needs sampling=\"request\", got "
+                f"sampling={sampling!r}")
         self._sampling_defaults = None
         self._sampling_counts = {"requests": 0, "sampled": 0, "greedy": 0}
         if sampling == "request":
@@ -1651,7 +1835,8 @@ class LlamaServer:
                                   top_k=engine_top_k,
                                   max_adapters=self.max_adapters,
                                   lora_rank=self.lora_rank,
-                                  sampling=self.sampling)
+                                  sampling=self.sampling,
+                                  logit_processors=self.logit_processors)
         self.engines = [first]
         for _ in range(self.replicas - 1):
             replica = LlamaDecodeEngine(
@@ -1659,7 +1844,8 @@ class LlamaServer:
                 use_graph=self.use_graph, weights=first.weights,
                 weight_dtype="bf16", kv_dtype=self.kv_dtype,
                 temperature=engine_temp, top_k=engine_top_k,
-                lora=first.lora, sampling=self.sampling)
+                lora=first.lora, sampling=self.sampling,
+                logit_processors=self.logit_processors)
             replica.weight_dtype = first.weight_dtype
             replica._fp8_packs = first._fp8_packs  # shared packs
             if first.weight_dtype == "fp8w" and replica.on_gpu:
@@ -2119,17 +2305,27 @@ class LlamaServer:
         is looked at).  Absent fields take the server's defaults, prompt
         j draws with seed + j, an absent seed is drawn at random.  A
         field out of range is a ValueError naming it, which fails this
-        request alone."""
+        request alone.  A logit_processors=True server also reads the
+        penalties and ``logit_bias`` and checks the bias ids against the
+        vocabulary here; without the flag those fields stay unread."""
         if self.sampling != "request":
             return None
         import dataclasses
         import random
 
         base = self._sampling_defaults
-        fields = {name: body[name] for name in
-                  ("temperature", "top_k", "top_p", "min_p", "seed",
-                   "logprobs") if body.get(name) is not None}
+        names = ("temperature", "top_k", "top_p", "min_p", "seed",
+                 "logprobs")
+        if self.logit_processors:
+            names += ("repetition_penalty", "presence_penalty",
+                      "frequency_penalty", "logit_bias")
+        fields = {name: body[name] for name in names
+                  if body.get(name) is not None}
         first = dataclasses.replace(base, **fields).validate()
+        if self.logit_processors:
+            # here, not at admission: a failure there would fail every
+            # request admitted together with this one
+            self.engine._check_processors(first)
         if "seed" not in fields:
             first.seed = random.SystemRandom().getrandbits(63)
         with self._lora_lock:

@@ -967,6 +967,139 @@ def sample_tokens(logits: torch.Tensor, pos: torch.Tensor,
     return out_tokens
 
 
+# ------------------------------------------------------ logit processors
+
+LOGIT_BIAS_MAX = 64            # bias entries per row
+LOGIT_TILE = 2048              # columns per workgroup of the kernel
+
+
+def _check_logit_processors(logits, state, penalties, bias_ids, bias_val,
+                            bias_n, tokens, rows):
+    """Argument checks of logit_processors; ValueError before any
+    launch."""
+    checks = [("logits", logits, torch.bfloat16),
+              ("state", state, torch.int32),
+              ("penalties", penalties, torch.float32),
+              ("bias_ids", bias_ids, torch.int32),
+              ("bias_val", bias_val, torch.float32),
+              ("bias_n", bias_n, torch.int32)]
+    if tokens is not None:
+        checks.append(("tokens", tokens, torch.int64))
+    if rows is not None:
+        checks.append(("rows", rows, torch.int32))
+    for name, tensor, dtype in checks:
+        if not isinstance(tensor, torch.Tensor):
+            raise ValueError(f"logit_processors: {name} must be a tensor")
+        if tensor.dtype != dtype:
+            raise ValueError(f"logit_processors: {name} must be {dtype}, "
+                             f"got {tensor.dtype}")
+        if not tensor.is_contiguous():
+            raise ValueError(f"logit_processors: {name} must be contiguous")
+        if tensor.device != logits.device:
+            raise ValueError(f"logit_processors: {name} is on "
+                             f"{tensor.device}, logits on {logits.device}")
+    if logits.dim() != 2:
+        raise ValueError("logit_processors: logits must be [B, V], got "
+                         f"{tuple(logits.shape)}")
+    B, V = logits.shape
+    if B > SAMPLE_MAX_ROWS:
+        raise ValueError(f"logit_processors: B must be <= "
+                         f"{SAMPLE_MAX_ROWS}, got {B}")
+    if V == 0 or V % 8 or V >= 1 << 24:
+        raise ValueError("logit_processors: logits [B, V] need V a positive "
+                         f"multiple of 8 below 2^24, got {V}")
+    if state.dim() != 2 or state.shape[1] != V:
+        raise ValueError(f"logit_processors: state must be [S, {V}], got "
+                         f"{tuple(state.shape)}")
+    shapes = [("penalties", penalties, (B, 3)),
+              ("bias_ids", bias_ids, (B, LOGIT_BIAS_MAX)),
+              ("bias_val", bias_val, (B, LOGIT_BIAS_MAX)),
+              ("bias_n", bias_n, (B,))]
+    if tokens is not None:
+        shapes.append(("tokens", tokens, (B,)))
+    if rows is not None:
+        shapes.append(("rows", rows, (B,)))
+    for name, tensor, shape in shapes:
+        if tuple(tensor.shape) != shape:
+            raise ValueError(f"logit_processors: {name} must be "
+                             f"{list(shape)}, got {tuple(tensor.shape)}")
+    if logits.is_cuda and (logits.data_ptr() % 16 or state.data_ptr() % 16):
+        raise ValueError("logit_processors: logits and state must be "
+                         "16-byte aligned (a view at an offset that is no "
+                         "multiple of 8 / 4 elements is not)")
+
+
+def logit_processors(logits: torch.Tensor, state: torch.Tensor,
+                     penalties: torch.Tensor, bias_ids: torch.Tensor,
+                     bias_val: torch.Tensor, bias_n: torch.Tensor,
+                     tokens: torch.Tensor = None,
+                     rows: torch.Tensor = None) -> torch.Tensor:
+    """Repetition, presence and frequency penalties and a logit bias,
+    applied in place to the logits a sampler reads next, from a token-
+    state table that the same call maintains.  Every parameter is a
+    tensor on the logits' device, read at run time: no allocation, no
+    sync, hipGraph-capture safe.
+
+    logits [B, V] bf16 (B <= 64, V % 8 == 0); state [S, V] int32 with
+    ``state[r, v] = 2 * n_out + in_prompt`` (how often sequence r has
+    generated token v, and whether its prompt holds it); penalties
+    [B, 3] f32, columns repetition r, presence p, frequency f; bias_ids
+    [B, 64] int32 and bias_val [B, 64] f32, of which the first
+    ``bias_n[b]`` (int32, clamped to [0, 64]) are live and an id outside
+    [0, V) is ignored; tokens [B] int64 or None, each row's pending
+    token (generated, not yet counted); rows [B] int32 or None, the
+    state row of logits row b (None: b).
+
+    A row with r == 1, p == 0, f == 0 and no live bias is neutral.  A
+    neutral row and a row whose state row is outside [0, S) are skipped
+    whole: logits and state untouched, the pending token not counted.
+    For every other row, in this order:
+    1. a pending token t in [0, V) is counted, state[row, t] += 2 (any
+       other t is ignored), before column t is evaluated;
+    2. per column v, c = state[row, v], n = c >> 1, z = float(logit):
+       c != 0 and r != 1: z = z / r if z > 0 else z * r
+       n > 0:             z = (z - f * float(n)) - p
+       v a live id:       z = z + bias_val
+       and the logit becomes bf16(z), rounded to nearest even.
+    Every step is one separately rounded f32 operation; this CPU branch
+    (torch elementwise ops) is the reference the kernel matches bit for
+    bit.  Two logits rows naming one state row are forbidden; of
+    duplicate live ids one value applies, unspecified which.  Bad
+    shapes, dtypes, layouts or devices raise ValueError before any
+    launch."""
+    _check_logit_processors(logits, state, penalties, bias_ids, bias_val,
+                            bias_n, tokens, rows)
+    if logits.is_cuda:
+        _require_hip().logit_processors(logits, state, penalties, bias_ids,
+                                        bias_val, bias_n, tokens, rows)
+        return logits
+    B, V = logits.shape
+    S = state.shape[0]
+    for b in range(B):
+        row = b if rows is None else int(rows[b])
+        rep, pres, freq = penalties[b]          # 0-dim f32 tensors
+        live = min(max(int(bias_n[b]), 0), LOGIT_BIAS_MAX)
+        if not 0 <= row < S:
+            continue
+        if rep == 1 and pres == 0 and freq == 0 and live == 0:
+            continue
+        counts = state[row]
+        if tokens is not None and 0 <= int(tokens[b]) < V:
+            counts[int(tokens[b])] += 2
+        z = logits[b].float()
+        if rep != 1:
+            z = torch.where((counts != 0) & (z > 0), z / rep,
+                            torch.where(counts != 0, z * rep, z))
+        n = counts >> 1
+        z = torch.where(n > 0, (z - freq * n.float()) - pres, z)
+        ids = bias_ids[b, :live].long()
+        inside = (ids >= 0) & (ids < V)
+        ids = ids[inside]
+        z[ids] = z[ids] + bias_val[b, :live][inside]
+        logits[b] = z.to(torch.bfloat16)
+    return logits
+
+
 def kv_append(k_cache, v_cache, k_new, v_new, positions):
     """Scatter the new token K/V into the cache at positions[b]."""
     if k_cache.is_cuda:

@@ -592,6 +592,62 @@ void sample_tokens(torch::Tensor logits, torch::Tensor pos,
                        (int)V, stream());
 }
 
+// penalties and logit bias in place on the logits, from the per-slot
+// token-state table that the same kernel maintains
+void logit_processors(torch::Tensor logits, torch::Tensor state,
+                      torch::Tensor penalties, torch::Tensor bias_ids,
+                      torch::Tensor bias_val, torch::Tensor bias_n,
+                      c10::optional<torch::Tensor> tokens,
+                      c10::optional<torch::Tensor> rows) {
+  CHECK_DEV(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
+  CHECK_DEV(state); CHECK_CONTIG(state); CHECK_I32(state);
+  CHECK_DEV(penalties); CHECK_CONTIG(penalties); CHECK_F32(penalties);
+  CHECK_DEV(bias_ids); CHECK_CONTIG(bias_ids); CHECK_I32(bias_ids);
+  CHECK_DEV(bias_val); CHECK_CONTIG(bias_val); CHECK_F32(bias_val);
+  CHECK_DEV(bias_n); CHECK_CONTIG(bias_n); CHECK_I32(bias_n);
+  TORCH_CHECK(logits.dim() == 2 && state.dim() == 2,
+              "logit_processors: logits must be [B, V], state [S, V]");
+  const int64_t B = logits.size(0), V = logits.size(1), S = state.size(0);
+  TORCH_CHECK(B <= 64, "logit_processors: at most 64 rows, got ", B);
+  TORCH_CHECK(V % 8 == 0 && V < (1LL << 24),
+              "logit_processors: V must be a multiple of 8 below 2^24, got ",
+              V);
+  TORCH_CHECK(state.size(1) == V,
+              "logit_processors: state must be [S, V] with the logits' V");
+  TORCH_CHECK(penalties.dim() == 2 && penalties.size(0) == B &&
+              penalties.size(1) == 3,
+              "logit_processors: penalties must be [B, 3]");
+  TORCH_CHECK(bias_ids.dim() == 2 && bias_ids.size(0) == B &&
+              bias_ids.size(1) == 64 && bias_val.dim() == 2 &&
+              bias_val.size(0) == B && bias_val.size(1) == 64,
+              "logit_processors: bias_ids and bias_val must be [B, 64]");
+  TORCH_CHECK(bias_n.numel() == B,
+              "logit_processors: bias_n must hold B entries");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(state.data_ptr()) % 16 == 0,
+              "logit_processors: logits and state must be 16-byte aligned");
+  const void* tokens_ptr = nullptr;
+  const void* rows_ptr = nullptr;
+  if (tokens.has_value()) {
+    CHECK_DEV(*tokens); CHECK_CONTIG(*tokens);
+    TORCH_CHECK(tokens->scalar_type() == torch::kInt64 &&
+                tokens->numel() == B,
+                "logit_processors: tokens must be int64 [B]");
+    tokens_ptr = tokens->data_ptr();
+  }
+  if (rows.has_value()) {
+    CHECK_DEV(*rows); CHECK_CONTIG(*rows); CHECK_I32(*rows);
+    TORCH_CHECK(rows->numel() == B,
+                "logit_processors: rows must hold B entries");
+    rows_ptr = rows->data_ptr();
+  }
+  if (B == 0 || S == 0) return;
+  launch_logit_processors(logits.data_ptr(), state.data_ptr(),
+                          penalties.data_ptr(), bias_ids.data_ptr(),
+                          bias_val.data_ptr(), bias_n.data_ptr(), tokens_ptr,
+                          rows_ptr, (int)B, (int)V, (int)S, stream());
+}
+
 void softmax(torch::Tensor out, torch::Tensor in) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(in); CHECK_CONTIG(in); CHECK_BF16(in);
@@ -763,6 +819,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_logprob") = py::none(),
         py::arg("out_kept") = py::none(),
         "fused seeded sampler: temperature, top_k, top_p, min_p, logprob");
+  m.def("logit_processors", &logit_processors, py::arg("logits"),
+        py::arg("state"), py::arg("penalties"), py::arg("bias_ids"),
+        py::arg("bias_val"), py::arg("bias_n"),
+        py::arg("tokens") = py::none(), py::arg("rows") = py::none(),
+        "repetition / presence / frequency penalties and logit bias, in "
+        "place, with the per-slot token counts");
   m.def("softmax", &softmax, "row softmax (bf16)");
   m.def("tree_ensemble", &tree_ensemble, "GBDT ensemble inference (f32)");
   m.def("window_ingest", &window_ingest,

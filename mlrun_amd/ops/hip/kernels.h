@@ -117,6 +117,12 @@ void launch_sample_tokens(const void* logits, const void* pos,
                           void* out_logprob, void* out_kept, int B, int V,
                           void* stream);
 
+void launch_logit_processors(void* logits, void* state,
+                             const void* penalties, const void* bias_ids,
+                             const void* bias_val, const void* bias_n,
+                             const void* tokens, const void* rows, int B,
+                             int V, int S, void* stream);
+
 void launch_softmax(void* out, const void* in, int rows, int cols,
                     void* stream);
 

@@ -3094,6 +3094,135 @@ void launch_sample_tokens(const void* logits, const void* pos,
 }
 
 // ---------------------------------------------------------------------
+// Logit processors: repetition / presence / frequency penalties and a
+// logit bias, applied in place to the logits a sampler reads next, from
+// a per-sequence token-state table that this kernel also maintains:
+//   state[r, v] = 2 * (times v was generated) + (v is in the prompt)
+// Grid (column tiles, B), 256 threads, 8 adjacent columns per thread: one
+// 16 B vector of logits and two of state.  Every logit and every state
+// word has exactly one owner, so there are no atomics and no thread
+// reads global memory that another wrote in this launch; the owner of
+// the pending token's column adds 2 to the word it holds and stores it.
+// A neutral row (r == 1, p == 0, f == 0, no live bias) and a row whose
+// state row is out of range leave before any load or barrier.
+// Per column, c = state word, n = c >> 1, z = float(logit):
+//   c != 0 and r != 1:  z = z > 0 ? z / r : z * r
+//   n > 0:              z = (z - f * float(n)) - p
+//   v is a live id:     z = z + bias
+// Each step is one separately rounded f32 operation, bit for bit what
+// ops.logit_processors computes on the CPU.  The build's default
+// contraction would fuse z - f * n into an fma, so contraction is
+// switched off for this kernel's body (#pragma clang fp contract(off))
+// rather than spelling every operation as an intrinsic.
+// Bias: wave 0 alone fills the LDS tile with -0.0f (z + -0.0f == z for
+// every z, -0.0f included) and then scatters the live entries of this
+// tile into it; LDS operations of one wave complete in issue order, so
+// one workgroup barrier publishes the tile.  Rows without live entries
+// skip tile and barrier, block-uniformly.
+// ---------------------------------------------------------------------
+constexpr int LOGIT_THREADS = 256;
+constexpr int LOGIT_TILE = LOGIT_THREADS * 8;
+constexpr int LOGIT_BIAS_MAX = 64;
+typedef __attribute__((ext_vector_type(4))) int int4v;
+
+__global__ __launch_bounds__(LOGIT_THREADS) void logit_processors_kernel(
+    unsigned short* __restrict__ logits, int* __restrict__ state,
+    const float* __restrict__ penalties, const int* __restrict__ bias_ids,
+    const float* __restrict__ bias_val, const int* __restrict__ bias_n,
+    const long long* __restrict__ tokens, const int* __restrict__ rows,
+    int V, int S) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) float tile[LOGIT_TILE];
+
+  const int b = blockIdx.y;
+  const int srow = rows ? rows[b] : b;
+  if (srow < 0 || srow >= S) return;  // block-uniform, before any barrier
+  const float rep = penalties[b * 3 + 0];
+  const float pres = penalties[b * 3 + 1];
+  const float freq = penalties[b * 3 + 2];
+  int live = bias_n[b];
+  live = live < 0 ? 0 : (live > LOGIT_BIAS_MAX ? LOGIT_BIAS_MAX : live);
+  if (rep == 1.f && pres == 0.f && freq == 0.f && live == 0) return;
+
+  const int tid = threadIdx.x;
+  const int base = blockIdx.x * LOGIT_TILE;
+  if (live > 0) {
+    if (tid < 64) {  // wave 0: LOGIT_BIAS_MAX == one wave
+      const f32x4v neg0 = {-0.f, -0.f, -0.f, -0.f};
+#pragma unroll
+      for (int i = 0; i < LOGIT_TILE / (64 * 4); ++i)
+        *reinterpret_cast<f32x4v*>(&tile[(i * 64 + tid) * 4]) = neg0;
+      // the scatter below may hit a word another lane has just filled
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (tid < live) {
+        const int id = bias_ids[b * LOGIT_BIAS_MAX + tid];
+        // id < V also keeps a last, partial tile inside the vocabulary
+        if (id >= base && id < base + LOGIT_TILE && id < V)
+          tile[id - base] = bias_val[b * LOGIT_BIAS_MAX + tid];
+      }
+    }
+    __syncthreads();
+  }
+  const int v = base + tid * 8;
+  if (v >= V) return;  // V % 8 == 0: a thread's 8 columns are in or out
+
+  unsigned short* lrow = logits + (size_t)b * V + v;
+  int* srow_ptr = state + (size_t)srow * V + v;
+  const short8v x = *reinterpret_cast<const short8v*>(lrow);
+  const int4v c_lo = *reinterpret_cast<const int4v*>(srow_ptr);
+  const int4v c_hi = *reinterpret_cast<const int4v*>(srow_ptr + 4);
+  int c[8] = {c_lo[0], c_lo[1], c_lo[2], c_lo[3],
+              c_hi[0], c_hi[1], c_hi[2], c_hi[3]};
+  // count the pending token first: its column is evaluated with it
+  const long long t = tokens ? tokens[b] : -1ll;
+  if (t >= (long long)v && t < (long long)v + 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (t == (long long)(v + j)) {
+        c[j] += 2;
+        srow_ptr[j] = c[j];
+      }
+    }
+  }
+  f32x4v add_lo = {-0.f, -0.f, -0.f, -0.f}, add_hi = add_lo;
+  if (live > 0) {
+    add_lo = *reinterpret_cast<const f32x4v*>(&tile[tid * 8]);
+    add_hi = *reinterpret_cast<const f32x4v*>(&tile[tid * 8 + 4]);
+  }
+  short8v y;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float z = bf2f((unsigned short)x[j]);
+    const int n = c[j] >> 1;
+    if (c[j] != 0 && rep != 1.f) z = z > 0.f ? z / rep : z * rep;
+    if (n > 0) {
+      const float scaled = freq * (float)n;
+      z = z - scaled;
+      z = z - pres;
+    }
+    if (live > 0) z = z + (j < 4 ? add_lo[j & 3] : add_hi[j & 3]);
+    y[j] = (short)f2bf(z);
+  }
+  *reinterpret_cast<short8v*>(lrow) = y;
+}
+
+void launch_logit_processors(void* logits, void* state,
+                             const void* penalties, const void* bias_ids,
+                             const void* bias_val, const void* bias_n,
+                             const void* tokens, const void* rows, int B,
+                             int V, int S, void* stream) {
+  if (B <= 0 || V <= 0 || S <= 0) return;
+  const dim3 grid((V + LOGIT_TILE - 1) / LOGIT_TILE, B);
+  hipLaunchKernelGGL(logit_processors_kernel, grid, dim3(LOGIT_THREADS), 0,
+                     (hipStream_t)stream, (unsigned short*)logits,
+                     (int*)state, (const float*)penalties,
+                     (const int*)bias_ids, (const float*)bias_val,
+                     (const int*)bias_n, (const long long*)tokens,
+                     (const int*)rows, V, S);
+}
+
+// ---------------------------------------------------------------------
 // Row softmax (bf16 in/out, online single pass over LDS-staged row,
 // used by classic-model servers & tests)
 // ---------------------------------------------------------------------
