@@ -28,6 +28,7 @@ import torch
 
 from .. import ops
 from ..utils import logger
+from .prefix_cache import PrefixIndex
 
 
 @dataclass
@@ -372,10 +373,23 @@ class LlamaDecodeEngine:
                  temperature: float = 0.0, top_k: int = 0,
                  max_adapters: int = 0, lora_rank: int = 16,
                  lora: "LoraTables" = None, sampling: str = "engine",
-                 logit_processors: bool = False):
+                 logit_processors: bool = False,
+                 prefix_cache_blocks: int = 0):
         if sampling not in ("engine", "request"):
             raise ValueError(f"unknown sampling mode {sampling!r} "
                              "(expected 'engine' or 'request')")
+        if prefix_cache_blocks < 0:
+            raise ValueError(
+                f"prefix_cache_blocks={prefix_cache_blocks} is negative")
+        if prefix_cache_blocks > 0 and kv_dtype == "fp8":
+            raise ValueError(
+                f"prefix_cache_blocks={prefix_cache_blocks} conflicts with "
+                'kv_dtype="fp8": the cache fills slots through packed '
+                "prefill, which needs a bf16 KV cache")
+        if prefix_cache_blocks > 0 and tp_size > 1:
+            raise ValueError(
+                f"prefix_cache_blocks={prefix_cache_blocks} conflicts with "
+                f"tp_size={tp_size}: the block pool is not sharded")
         if logit_processors and sampling != "request":
             raise ValueError(
                 f"logit_processors=True needs sampling=\"request\", got "
@@ -563,6 +577,38 @@ class LlamaDecodeEngine:
             self.buf_bias_n = torch.zeros(B, dtype=torch.int32, device=dev)
         # speculative decoding (opt-in): running acceptance counters
         self.spec_stats = {"steps": 0, "drafted": 0, "accepted": 0}
+        # prefix cache (opt-in): a pool of 32-token KV blocks
+        # [L, N, Hkv, 32, D] kept between requests, and the host index
+        # that names their content.  prefill_cached copies hit blocks
+        # into the slot and prefills the rest.  At 0 nothing is allocated.
+        self.prefix_index = None
+        self.pc_k = self.pc_v = None
+        if prefix_cache_blocks > 0:
+            if not self._packed_prefill_serves():
+                raise ValueError(
+                    f"prefix_cache_blocks={prefix_cache_blocks} conflicts "
+                    f"with head_dim={d} and {w.hq}/{w.hkv} q/kv heads: "
+                    "packed prefill serves head_dim 128 and at most 8 "
+                    "q-heads per KV head")
+            self.prefix_index = PrefixIndex(prefix_cache_blocks)
+            self.pc_k = torch.zeros(cfg.num_layers, prefix_cache_blocks,
+                                    w.hkv, ops.KV_BLOCK_TOKENS, d, **bf16)
+            self.pc_v = torch.zeros_like(self.pc_k)
+
+    # ---------------------------------------------------- prefix cache
+    def clear_prefix_cache(self):
+        """Forget every cached prefix (the pool's memory stays)."""
+        if self.prefix_index is not None:
+            self.prefix_index.clear()
+
+    @property
+    def prefix_stats(self) -> dict:
+        """Counters of the prefix cache: lookups, prompt_tokens,
+        hit_tokens, inserted, evicted, blocks_in_use, capacity."""
+        if self.prefix_index is None:
+            raise ValueError("engine built with prefix_cache_blocks=0 "
+                             "holds no prefix cache")
+        return self.prefix_index.stats()
 
     # -------------------------------------------------------- sampling
     def set_sampling(self, slot: int, temperature: float = 0.0,
@@ -769,6 +815,8 @@ class LlamaDecodeEngine:
             raise ValueError("engine built with max_adapters=0 holds no "
                              "adapter tables")
         self.lora.load(slot, state)
+        # cached KV rows of this table slot are stale now
+        self.clear_prefix_cache()
 
     def unload_adapter(self, slot: int):
         """Zero table slot ``slot`` (idle engine only, like
@@ -777,6 +825,7 @@ class LlamaDecodeEngine:
             raise ValueError("engine built with max_adapters=0 holds no "
                              "adapter tables")
         self.lora.unload(slot)
+        self.clear_prefix_cache()
 
     def _lora_decode(self, li, proj, x, y):
         """y[b] += Bm[id_b] (A[id_b] x[b]) for the decode rows, by
@@ -784,6 +833,26 @@ class LlamaDecodeEngine:
         a_tab, b_tab = self.lora.layers[li][proj]
         ops.lora_shrink(x, a_tab, self.buf_adapter, out=self.buf_lora_t)
         ops.lora_expand(y, self.buf_lora_t, b_tab, self.buf_adapter)
+
+    def _adapter_ids(self, adapters, n):
+        """Validate ``adapters`` (not None): one id per prompt for ``n``
+        prompts, each in [-1, max_adapters).  Returns the ids, or None
+        on an engine without adapter tables (where every id must be
+        -1)."""
+        ids = [int(a) for a in adapters]
+        if self.lora is None:
+            if any(a >= 0 for a in ids):
+                raise ValueError("adapters= needs an engine built with "
+                                 "max_adapters > 0")
+            return None
+        if len(ids) != n:
+            raise ValueError(f"adapters has {len(ids)} ids for "
+                             f"{n} prompts")
+        for a in ids:
+            if not -1 <= a < self.max_adapters:
+                raise ValueError(f"adapter id {a} outside "
+                                 f"[-1, {self.max_adapters})")
+        return ids
 
     def _adapter_plan(self, adapters, slots, counts):
         """Prefill side of ``adapters=``: validate one id per prompt
@@ -796,19 +865,9 @@ class LlamaDecodeEngine:
             if self.lora is not None:
                 self.buf_adapter[slots] = -1
             return None
-        ids = [int(a) for a in adapters]
-        if self.lora is None:
-            if any(a >= 0 for a in ids):
-                raise ValueError("adapters= needs an engine built with "
-                                 "max_adapters > 0")
+        ids = self._adapter_ids(adapters, len(counts))
+        if ids is None:
             return None
-        if len(ids) != len(counts):
-            raise ValueError(f"adapters has {len(ids)} ids for "
-                             f"{len(counts)} prompts")
-        for a in ids:
-            if not -1 <= a < self.max_adapters:
-                raise ValueError(f"adapter id {a} outside "
-                                 f"[-1, {self.max_adapters})")
         self.buf_adapter[slots] = torch.tensor(
             ids, dtype=torch.int32).to(self.device)
         distinct = sorted({a for a in ids if a >= 0})
@@ -1296,7 +1355,14 @@ class LlamaDecodeEngine:
         last-token logits [n, vocab]; sets cache_lens and buf_tokens
         for the slots like ``prefill_slots``.  bf16 KV caches only.
         ``adapters``: one LoRA table slot per prompt (-1 = base)."""
-        cfg, w = self.cfg, self.weights
+        return self._packed_pass(
+            *self._check_packed(prompts, slots, starts), adapters)
+
+    def _check_packed(self, prompts, slots, starts=None):
+        """The argument checks of a packed pass, all on the host and
+        before any device work.  Returns (prompts, slots, starts) as
+        lists of ints."""
+        cfg = self.cfg
         if self.kv_dtype == "fp8":
             raise ValueError("packed prefill needs a bf16 KV cache")
         prompts = [[int(t) for t in p] for p in prompts]
@@ -1328,6 +1394,20 @@ class LlamaDecodeEngine:
                 raise ValueError(
                     f"sequence of {start}+{length} tokens would reach "
                     f"max_seq_len {cfg.max_seq_len}")
+        return prompts, slot_list, start_list
+
+    def _packed_pass(self, prompts, slot_list, start_list, adapters,
+                     whole=None):
+        """The packed pass over checked arguments (_check_packed).
+        ``whole`` is None for a plain prefill_packed call, where a chunk
+        with starts[i] > 0 continues a sequence and adds only its own
+        tokens to the slot's token state.  prefill_cached passes the
+        full prompts there: its chunks are the uncached ends of FRESH
+        requests, whose every token, the cached ones too, counts as
+        in the prompt."""
+        cfg, w = self.cfg, self.weights
+        n = len(prompts)
+        lens = [len(p) for p in prompts]
         d = cfg.head_dim
         T = sum(lens)
         # one host->device copy for all the int32 index vectors
@@ -1363,9 +1443,68 @@ class LlamaDecodeEngine:
             cu_seqlens[1:] - cu_seqlens[:-1])
         last = hidden[cu_seqlens[1:].long() - 1]
         logits = last @ w.lm_head.t()
-        self._first_tokens(logits, slots_long, (
-            tok_slot.long(), tokens, kv_start == 0))
+        if whole is not None and self.logit_processors:
+            state = torch.tensor(
+                [slot for slot, p in zip(slot_list, whole) for _ in p]
+                + [t for p in whole for t in p],
+                dtype=torch.int64).to(self.device)
+            prompt = (*state.split(state.numel() // 2), None)
+        else:
+            prompt = (tok_slot.long(), tokens, kv_start == 0)
+        self._first_tokens(logits, slots_long, prompt)
         return logits
+
+    @torch.no_grad()
+    def prefill_cached(self, prompts, slots, adapters=None) -> torch.Tensor:
+        """prefill_packed through the prefix cache (engines built with
+        ``prefix_cache_blocks > 0``): the same arguments, the same
+        result and slot state, but the leading 32-token blocks of a
+        prompt whose KV rows are in the pool are copied into the slot
+        and only the rest is prefilled.
+
+        One ``ops.kv_block_copy`` gathers every hit block of the call,
+        one packed pass runs over the uncached ends with ``starts`` =
+        the hit lengths, and one more ``kv_block_copy`` stores the
+        prompts' new full blocks from the slots into the pool, all on
+        the current stream.  A hit is on content: every token up to the
+        block's end and the adapter id are equal.  At least one token
+        of a prompt is always prefilled.  A call that fails its checks
+        changes nothing, in the slots or in the cache."""
+        index = self.prefix_index
+        if index is None:
+            raise ValueError("prefill_cached needs an engine built with "
+                             "prefix_cache_blocks > 0")
+        prompts, slot_list, _ = self._check_packed(prompts, slots)
+        ids = None if adapters is None else \
+            self._adapter_ids(adapters, len(prompts))
+        keys = ids if ids is not None else [-1] * len(prompts)
+        BT = ops.KV_BLOCK_TOKENS
+        index.begin()
+        hits = [index.lookup(p, key) for p, key in zip(prompts, keys)]
+        self._copy_blocks(
+            [(block, 0, slot, j) for slot, chain in zip(slot_list, hits)
+             for j, block in enumerate(chain)], to_pool=False)
+        starts = [len(chain) * BT for chain in hits]
+        logits = self._packed_pass(
+            [p[start:] for p, start in zip(prompts, starts)],
+            slot_list, starts, adapters, whole=prompts)
+        self._copy_blocks(
+            [(slot, j, block, 0)
+             for p, key, slot in zip(prompts, keys, slot_list)
+             for j, block in index.insert(p, key)], to_pool=True)
+        return logits
+
+    def _copy_blocks(self, entries, to_pool):
+        """One ops.kv_block_copy over ``entries`` =
+        [(src row, src block, dst row, dst block)], pool -> cache or
+        cache -> pool; nothing is launched for an empty list."""
+        if not entries:
+            return
+        rows = torch.tensor(entries, dtype=torch.int32).t().contiguous(
+            ).to(self.device)
+        pool, cache = (self.pc_k, self.pc_v), (self.k_cache, self.v_cache)
+        src, dst = (cache, pool) if to_pool else (pool, cache)
+        ops.kv_block_copy(*src, *dst, rows[0], rows[1], rows[2], rows[3])
 
     # -------------------------------------------------------- generate
     @torch.no_grad()
@@ -1649,6 +1788,13 @@ class LlamaServer:
       applies them, in that order, with ``ops.logit_processors`` before
       every draw; logprobs are then those of the processed logits.
       Without the flag the four fields are not read.
+    - ``prefix_cache_blocks``: N > 0 gives every replica a pool of N
+      32-token KV blocks; admission then goes through
+      ``engine.prefill_cached``, which copies the cached leading blocks
+      of a prompt into its slot and prefills the rest, in both
+      schedulers and whatever ``prefill`` says.  Each replica has its
+      own pool: a prefix cached on one misses on another.  Not with
+      ``kv_dtype="fp8"`` or ``speculative > 0``.  Default 0 = off.
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -1661,7 +1807,8 @@ class LlamaServer:
                  adapters: dict = None, max_adapters: int = None,
                  lora_rank: int = 16, sampling: str = "engine",
                  top_p: float = 1.0, min_p: float = 0.0,
-                 logit_processors: bool = False, **class_args):
+                 logit_processors: bool = False,
+                 prefix_cache_blocks: int = 0, **class_args):
         import queue as queue_mod
         import threading
 
@@ -1733,6 +1880,20 @@ class LlamaServer:
                 temperature=temperature, top_k=top_k, top_p=top_p,
                 min_p=min_p).validate()
         self._check_speculative_config()
+        # prefix cache: N pool blocks of 32 tokens per replica (0 = off)
+        self.prefix_cache_blocks = int(prefix_cache_blocks)
+        if self.prefix_cache_blocks < 0:
+            raise ValueError(
+                f"prefix_cache_blocks={prefix_cache_blocks} is negative")
+        if self.prefix_cache_blocks > 0 and kv_dtype == "fp8":
+            raise ValueError(
+                f"prefix_cache_blocks={prefix_cache_blocks} conflicts with "
+                'kv_dtype="fp8": cached prefixes are bf16 KV rows')
+        if self.prefix_cache_blocks > 0 and self.speculative > 0:
+            raise ValueError(
+                f"prefix_cache_blocks={prefix_cache_blocks} conflicts with "
+                f"speculative={self.speculative}: the speculative path "
+                "prefills without the cache")
         self.replicas = max(int(replicas), 1)
         self.engines: typing.List[LlamaDecodeEngine] = []
         self.batch_window_ms = batch_window_ms
@@ -1836,7 +1997,8 @@ class LlamaServer:
                                   max_adapters=self.max_adapters,
                                   lora_rank=self.lora_rank,
                                   sampling=self.sampling,
-                                  logit_processors=self.logit_processors)
+                                  logit_processors=self.logit_processors,
+                                  prefix_cache_blocks=self.prefix_cache_blocks)
         self.engines = [first]
         for _ in range(self.replicas - 1):
             replica = LlamaDecodeEngine(
@@ -1845,7 +2007,8 @@ class LlamaServer:
                 weight_dtype="bf16", kv_dtype=self.kv_dtype,
                 temperature=engine_temp, top_k=engine_top_k,
                 lora=first.lora, sampling=self.sampling,
-                logit_processors=self.logit_processors)
+                logit_processors=self.logit_processors,
+                prefix_cache_blocks=self.prefix_cache_blocks)
             replica.weight_dtype = first.weight_dtype
             replica._fp8_packs = first._fp8_packs  # shared packs
             if first.weight_dtype == "fp8w" and replica.on_gpu:
@@ -1999,6 +2162,9 @@ class LlamaServer:
         by_request = engine.sampling == "request"
         lp_ring = torch.empty(B, ring_len, dtype=torch.float32,
                               device=engine.device) if by_request else None
+        # prefix cache on: every admission group goes through
+        # prefill_cached, whatever ``prefill`` says
+        cached = engine.prefix_index is not None
 
         def emit(state, token, logprob):
             """One streamed token, with its logprob when asked for."""
@@ -2077,19 +2243,23 @@ class LlamaServer:
                         with stream_ctx():
                             engine.set_sampling_slots(admit_slots,
                                                       admit_params)
-                    if self.prefill == "packed":
+                    if self.prefill == "packed" or cached:
                         # the whole mixed-length group in ONE pass:
                         # packed rows carry no padding, so the result
-                        # is independent of co-arriving traffic too
+                        # is independent of co-arriving traffic too.
+                        # With the prefix cache on, the same pass after
+                        # the cached blocks were copied into the slots.
                         by_len = {}
                         slot_ids = torch.tensor(admit_slots,
                                                 dtype=torch.long)
+                        admit = engine.prefill_cached if cached \
+                            else engine.prefill_packed
                         with stream_ctx():
                             if lora_on:
-                                engine.prefill_packed(prompts, admit_slots,
-                                                      adapters=admit_ids)
+                                admit(prompts, admit_slots,
+                                      adapters=admit_ids)
                             else:
-                                engine.prefill_packed(prompts, admit_slots)
+                                admit(prompts, admit_slots)
                             out_ring[slot_ids, step % ring_len] = \
                                 engine.buf_tokens[slot_ids]
                             if by_request:
@@ -2437,6 +2607,14 @@ class LlamaServer:
         lora_on = engine.lora is not None
         if lora_on:
             engine.buf_adapter.fill_(-1)  # rows beyond n run the base
+        if engine.prefix_index is not None:
+            # prefix cache on: rows 0..n-1 in ONE pass over what the
+            # pool does not hold (packed rows carry no padding either)
+            by_len = {}
+            if lora_on and adapters is not None:
+                engine.prefill_cached(prompts, range(n), adapters=adapters)
+            else:
+                engine.prefill_cached(prompts, range(n))
         for length, idxs in by_len.items():
             tokens = torch.tensor([prompts[i] for i in idxs],
                                   dtype=torch.int64)
@@ -2505,6 +2683,23 @@ class LlamaServer:
         return request.get("inputs"), None
 
     def stats(self):
+        out = self._feature_stats()
+        if self.prefix_cache_blocks > 0:
+            # summed over the replicas, each of which has its own pool
+            names = (("requests", "lookups"),
+                     ("prompt_tokens", "prompt_tokens"),
+                     ("hit_tokens", "hit_tokens"),
+                     ("blocks", "blocks_in_use"), ("capacity", "capacity"),
+                     ("evictions", "evicted"))
+            totals = {key: 0 for key, _ in names}
+            for engine in self.engines:
+                counters = engine.prefix_stats
+                for key, source in names:
+                    totals[key] += counters[source]
+            out["prefix_cache"] = totals
+        return out
+
+    def _feature_stats(self):
         if self.sampling == "request":
             with self._lora_lock:
                 out = {"sampling": dict(self._sampling_counts)}

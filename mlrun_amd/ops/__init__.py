@@ -525,6 +525,82 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor,
     return out
 
 
+# ---------------------------------------------------------- prefix cache
+
+KV_BLOCK_TOKENS = 32    # rows of one prefix-cache block
+
+
+def kv_block_copy(src_k: torch.Tensor, src_v: torch.Tensor,
+                  dst_k: torch.Tensor, dst_v: torch.Tensor,
+                  src_row: torch.Tensor, src_blk: torch.Tensor,
+                  dst_row: torch.Tensor, dst_blk: torch.Tensor):
+    """Copy 32-token KV blocks between two bf16 tensors
+    src [L, Rs, Hkv, Ss, D] and dst [L, Rd, Hkv, Sd, D]: entry i moves
+    rows [src_blk[i]*32, +32) of src[:, src_row[i]] to rows
+    [dst_blk[i]*32, +32) of dst[:, dst_row[i]], for every layer and KV
+    head, K and V, in ONE launch.  The prefix-cache pool is
+    [L, N, Hkv, 32, D] (block index 0) and the engine cache
+    [L, B, Hkv, Smax, D], so the same op gathers pool -> slot and
+    scatters slot -> pool.  The four index vectors are int32 [n].  An
+    entry whose row is out of range, or whose block would reach past Ss
+    or Sd, is skipped as a whole.  The caller keeps destinations
+    distinct."""
+    tensors = (("src_k", src_k), ("src_v", src_v),
+               ("dst_k", dst_k), ("dst_v", dst_v))
+    indices = (("src_row", src_row), ("src_blk", src_blk),
+               ("dst_row", dst_row), ("dst_blk", dst_blk))
+    device = src_k.device
+    for name, t in tensors:
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{name} must be bf16, got {t.dtype}")
+        if t.dim() != 5:
+            raise ValueError(f"{name} must be [L, R, Hkv, S, D], got "
+                             f"{t.dim()} dimensions")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device != device:
+            raise ValueError(f"{name} is on {t.device}, src_k on {device}")
+    if src_v.shape != src_k.shape or dst_v.shape != dst_k.shape:
+        raise ValueError("K and V must have equal shapes: src "
+                         f"{tuple(src_k.shape)}/{tuple(src_v.shape)}, dst "
+                         f"{tuple(dst_k.shape)}/{tuple(dst_v.shape)}")
+    L, Rs, Hkv, Ss, D = src_k.shape
+    Rd, Sd = dst_k.shape[1], dst_k.shape[3]
+    if (dst_k.shape[0], dst_k.shape[2], dst_k.shape[4]) != (L, Hkv, D):
+        raise ValueError(f"src {tuple(src_k.shape)} and dst "
+                         f"{tuple(dst_k.shape)} differ in L, Hkv or D")
+    if (D * 2) % 16 != 0:
+        raise ValueError(f"head dim {D}: rows must be a multiple of 16 "
+                         "bytes")
+    n = src_row.numel()
+    for name, t in indices:
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise ValueError(f"{name} must be a 1-d int32 tensor")
+        if t.device != device:
+            raise ValueError(f"{name} is on {t.device}, src_k on {device}")
+        if t.numel() != n:
+            raise ValueError(f"{name} has {t.numel()} entries, src_row "
+                             f"{n}")
+    if n == 0:
+        return
+    if src_k.is_cuda:
+        _require_hip().kv_block_copy(
+            src_k, src_v, dst_k, dst_v, src_row.contiguous(),
+            src_blk.contiguous(), dst_row.contiguous(),
+            dst_blk.contiguous())
+        return
+    BT = KV_BLOCK_TOKENS
+    for sr, sb, dr, db in zip(src_row.tolist(), src_blk.tolist(),
+                              dst_row.tolist(), dst_blk.tolist()):
+        if not (0 <= sr < Rs and 0 <= dr < Rd and sb >= 0 and db >= 0
+                and (sb + 1) * BT <= Ss and (db + 1) * BT <= Sd):
+            continue
+        dst_k[:, dr, :, db * BT:(db + 1) * BT] = \
+            src_k[:, sr, :, sb * BT:(sb + 1) * BT]
+        dst_v[:, dr, :, db * BT:(db + 1) * BT] = \
+            src_v[:, sr, :, sb * BT:(sb + 1) * BT]
+
+
 # -------------------------------------------------- speculative decoding
 
 VERIFY_MAX_QL = 8       # query rows per sequence in one verify pass

@@ -6,6 +6,8 @@
 // Torch bindings for the CDNA4 kernel library (mlrun_amd._hip_ops).
 // Thin validation + launch layer; kernels live in kernels.hip.
 
+#include <climits>
+
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
@@ -366,6 +368,48 @@ void rope_kv_varlen(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc,
                         positions.data_ptr(), tok_slot.data_ptr(),
                         cos_sin.data_ptr(), (int)T, B, (int)hq, Hkv, Smax, D,
                         (int)cos_sin.size(0), qkv.size(1), stream());
+}
+
+// prefix cache: copy 32-token KV blocks src[:, src_row, :, src_blk*32..]
+// -> dst[:, dst_row, :, dst_blk*32..] for every layer and KV head
+void kv_block_copy(torch::Tensor src_k, torch::Tensor src_v,
+                   torch::Tensor dst_k, torch::Tensor dst_v,
+                   torch::Tensor src_row, torch::Tensor src_blk,
+                   torch::Tensor dst_row, torch::Tensor dst_blk) {
+  CHECK_DEV(src_k); CHECK_CONTIG(src_k); CHECK_BF16(src_k);
+  CHECK_DEV(src_v); CHECK_CONTIG(src_v); CHECK_BF16(src_v);
+  CHECK_DEV(dst_k); CHECK_CONTIG(dst_k); CHECK_BF16(dst_k);
+  CHECK_DEV(dst_v); CHECK_CONTIG(dst_v); CHECK_BF16(dst_v);
+  CHECK_DEV(src_row); CHECK_CONTIG(src_row); CHECK_I32(src_row);
+  CHECK_DEV(src_blk); CHECK_CONTIG(src_blk); CHECK_I32(src_blk);
+  CHECK_DEV(dst_row); CHECK_CONTIG(dst_row); CHECK_I32(dst_row);
+  CHECK_DEV(dst_blk); CHECK_CONTIG(dst_blk); CHECK_I32(dst_blk);
+  TORCH_CHECK(src_k.dim() == 5 && src_v.sizes() == src_k.sizes(),
+              "src must be [L, Rs, Hkv, Ss, D] of equal shape");
+  TORCH_CHECK(dst_k.dim() == 5 && dst_v.sizes() == dst_k.sizes(),
+              "dst must be [L, Rd, Hkv, Sd, D] of equal shape");
+  int64_t L = src_k.size(0), Hkv = src_k.size(2), D = src_k.size(4);
+  TORCH_CHECK(dst_k.size(0) == L && dst_k.size(2) == Hkv &&
+              dst_k.size(4) == D, "src/dst L, Hkv, D must match");
+  TORCH_CHECK(D % 8 == 0, "head_dim * 2 bytes must be a multiple of 16");
+  TORCH_CHECK(L * Hkv >= 1 && L * Hkv <= 65535, "too many layers*heads");
+  int64_t n = src_row.numel();
+  TORCH_CHECK(src_row.dim() == 1 && src_blk.dim() == 1 &&
+              dst_row.dim() == 1 && dst_blk.dim() == 1 &&
+              src_blk.numel() == n && dst_row.numel() == n &&
+              dst_blk.numel() == n,
+              "index vectors must be 1-d of equal length");
+  TORCH_CHECK(src_k.size(1) <= INT_MAX && src_k.size(3) <= INT_MAX &&
+              dst_k.size(1) <= INT_MAX && dst_k.size(3) <= INT_MAX &&
+              n <= INT_MAX, "dimension too large");
+  if (n == 0) return;
+  launch_kv_block_copy(src_k.data_ptr(), src_v.data_ptr(), dst_k.data_ptr(),
+                       dst_v.data_ptr(), src_row.data_ptr(),
+                       src_blk.data_ptr(), dst_row.data_ptr(),
+                       dst_blk.data_ptr(), (int)n, (int)L, (int)Hkv,
+                       (int)src_k.size(1), (int)src_k.size(3),
+                       (int)dst_k.size(1), (int)dst_k.size(3), (int)D,
+                       stream());
 }
 
 // packed prefill: causal GQA flash attention over the slot-indexed cache
@@ -794,6 +838,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vc"), py::arg("positions"), py::arg("tok_slot"),
         py::arg("cos_sin"), py::arg("hq"),
         "packed-prefill rope(q,k) + KV append by per-token slot");
+  m.def("kv_block_copy", &kv_block_copy, py::arg("src_k"),
+        py::arg("src_v"), py::arg("dst_k"), py::arg("dst_v"),
+        py::arg("src_row"), py::arg("src_blk"), py::arg("dst_row"),
+        py::arg("dst_blk"),
+        "prefix cache: copy 32-token KV blocks between pool and cache");
   m.def("attn_prefill", &attn_prefill, py::arg("o"), py::arg("q"),
         py::arg("kc"), py::arg("vc"), py::arg("cu_seqlens"),
         py::arg("slots"), py::arg("kv_start"), py::arg("scale"),

@@ -85,6 +85,13 @@ void launch_rope_kv_varlen(void* qkv, void* Kc, void* Vc,
                            int Hkv, int Smax, int D, int max_pos,
                            long long row_stride, void* stream);
 
+void launch_kv_block_copy(const void* srcK, const void* srcV, void* dstK,
+                          void* dstV, const void* src_row,
+                          const void* src_blk, const void* dst_row,
+                          const void* dst_blk, int n, int L, int Hkv,
+                          int Rs, int Ss, int Rd, int Sd, int D,
+                          void* stream);
+
 void launch_attn_prefill(void* O, const void* Q, const void* Kc,
                          const void* Vc, const void* cu_seqlens,
                          const void* slots, const void* kv_start, int T,

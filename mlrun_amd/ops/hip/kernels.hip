@@ -2087,6 +2087,68 @@ void launch_rope_kv_varlen(void* qkv, void* Kc, void* Vc,
 }
 
 // ---------------------------------------------------------------------
+// Prefix cache: copy 32-token KV blocks between two 5-d bf16 tensors,
+// src [L, Rs, Hkv, Ss, D] -> dst [L, Rd, Hkv, Sd, D].  Entry e moves rows
+// [src_blk[e]*32, +32) of src[:, src_row[e]] to rows [dst_blk[e]*32, +32)
+// of dst[:, dst_row[e]], for every layer and KV head, K and V alike.
+// The block pool is [L, N, Hkv, 32, D] and the engine cache
+// [L, B, Hkv, Smax, D], so one kernel gathers (pool -> slot) and
+// scatters (slot -> pool).  The 32 rows of one (layer, row, head) are
+// contiguous: a workgroup copies 32*D*2 bytes per tensor in 16-byte
+// pieces.  All element offsets are 64-bit (an 8B cache passes 2^31).
+// grid: (n, L*Hkv); block: 256 threads.
+// An entry whose row is out of range, or whose block would reach past
+// Ss or Sd, is left untouched as a whole.  Destinations are distinct.
+// ---------------------------------------------------------------------
+constexpr int KV_BLOCK_TOKENS = 32;
+
+__global__ void kv_block_copy_kernel(
+    const unsigned short* __restrict__ srcK,
+    const unsigned short* __restrict__ srcV,
+    unsigned short* __restrict__ dstK, unsigned short* __restrict__ dstV,
+    const int* __restrict__ src_row, const int* __restrict__ src_blk,
+    const int* __restrict__ dst_row, const int* __restrict__ dst_blk,
+    int Hkv, int Rs, int Ss, int Rd, int Sd, int D) {
+  const int e = blockIdx.x;
+  const int layer = blockIdx.y / Hkv;
+  const int kvh = blockIdx.y % Hkv;
+  const int sr = src_row[e], sb = src_blk[e];
+  const int dr = dst_row[e], db = dst_blk[e];
+  if ((unsigned)sr >= (unsigned)Rs || (unsigned)dr >= (unsigned)Rd ||
+      sb < 0 || db < 0 ||
+      ((long long)sb + 1) * KV_BLOCK_TOKENS > (long long)Ss ||
+      ((long long)db + 1) * KV_BLOCK_TOKENS > (long long)Sd)
+    return;
+  const size_t src =
+      ((((size_t)layer * Rs + sr) * Hkv + kvh) * Ss +
+       (size_t)sb * KV_BLOCK_TOKENS) * D;
+  const size_t dst =
+      ((((size_t)layer * Rd + dr) * Hkv + kvh) * Sd +
+       (size_t)db * KV_BLOCK_TOKENS) * D;
+  const int elems = KV_BLOCK_TOKENS * D;  // D % 8 == 0 (host-checked)
+  for (int i = threadIdx.x * 8; i < elems; i += blockDim.x * 8) {
+    *reinterpret_cast<ushort8*>(dstK + dst + i) =
+        *reinterpret_cast<const ushort8*>(srcK + src + i);
+    *reinterpret_cast<ushort8*>(dstV + dst + i) =
+        *reinterpret_cast<const ushort8*>(srcV + src + i);
+  }
+}
+
+void launch_kv_block_copy(const void* srcK, const void* srcV, void* dstK,
+                          void* dstV, const void* src_row,
+                          const void* src_blk, const void* dst_row,
+                          const void* dst_blk, int n, int L, int Hkv,
+                          int Rs, int Ss, int Rd, int Sd, int D,
+                          void* stream) {
+  hipLaunchKernelGGL(kv_block_copy_kernel, dim3(n, L * Hkv), dim3(256), 0,
+                     (hipStream_t)stream, (const unsigned short*)srcK,
+                     (const unsigned short*)srcV, (unsigned short*)dstK,
+                     (unsigned short*)dstV, (const int*)src_row,
+                     (const int*)src_blk, (const int*)dst_row,
+                     (const int*)dst_blk, Hkv, Rs, Ss, Rd, Sd, D);
+}
+
+// ---------------------------------------------------------------------
 // Packed (varlen) prefill, part 2: causal GQA flash-attention forward
 // over the slot-indexed KV cache.
 //
