@@ -57,9 +57,12 @@ def fused_add_rmsnorm(x: torch.Tensor, weight: torch.Tensor,
         return out
     # fp32 reference
     z = x.float() + (residual.float() if residual is not None else 0.0)
-    if residual is not None:
-        residual.copy_(z.to(residual.dtype))
     var = z.pow(2).mean(dim=-1, keepdim=True)
+    if residual is not None:
+        # as the kernel does: the sum of squares takes the fp32 sum,
+        # the normalization the new residual as stored
+        residual.copy_(z.to(residual.dtype))
+        z = residual.float()
     result = (z * torch.rsqrt(var + eps)) * weight.float()
     result = result.to(x.dtype)
     if out is not None:

@@ -155,6 +155,9 @@ void fused_add_rmsnorm_slab(torch::Tensor out, torch::Tensor residual,
   int64_t hidden = out.size(-1);
   int64_t rows = out.numel() / hidden;
   TORCH_CHECK(hidden % 8 == 0, "hidden must be a multiple of 8");
+  TORCH_CHECK(ksplit >= 1, "ksplit must be at least 1");
+  TORCH_CHECK(residual.numel() == out.numel(), "residual size mismatch");
+  TORCH_CHECK(weight.numel() == hidden, "weight size mismatch");
   TORCH_CHECK(slabs.numel() >= ksplit * rows * hidden, "slabs too small");
   launch_fused_add_rmsnorm_slab(out.data_ptr(), residual.data_ptr(),
                                 slabs.data_ptr(), weight.data_ptr(),
@@ -165,6 +168,8 @@ void fused_add_rmsnorm_slab(torch::Tensor out, torch::Tensor residual,
 void swiglu_slab(torch::Tensor out, torch::Tensor slabs, int64_t ksplit) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(slabs); CHECK_CONTIG(slabs); CHECK_F32(slabs);
+  TORCH_CHECK(out.dim() == 2, "out must be [rows, inter]");
+  TORCH_CHECK(ksplit >= 1, "ksplit must be at least 1");
   int rows = out.size(0), inter = out.size(1);
   TORCH_CHECK(inter % 4 == 0, "inter must be a multiple of 4");
   TORCH_CHECK(slabs.numel() >= (int64_t)ksplit * rows * 2 * inter,
@@ -178,13 +183,22 @@ void rope_kv_slab(torch::Tensor qkv, torch::Tensor kc, torch::Tensor vc,
                   torch::Tensor cos_sin, int64_t hq, int64_t ksplit) {
   CHECK_DEV(qkv); CHECK_CONTIG(qkv); CHECK_BF16(qkv);
   CHECK_DEV(kc); CHECK_CONTIG(kc); CHECK_BF16(kc);
+  CHECK_DEV(vc); CHECK_CONTIG(vc); CHECK_BF16(vc);
   CHECK_DEV(slabs); CHECK_CONTIG(slabs); CHECK_F32(slabs);
   CHECK_DEV(positions); CHECK_CONTIG(positions); CHECK_I32(positions);
   CHECK_DEV(cos_sin); CHECK_CONTIG(cos_sin); CHECK_F32(cos_sin);
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes(),
+              "caches must be [B, Hkv, Smax, D] of equal shape");
   int B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
+  TORCH_CHECK(qkv.dim() == 2, "qkv must be [B, rows]");
   int qkv_row = qkv.size(1);
-  TORCH_CHECK(qkv.size(0) == B && qkv_row >= (hq + 2 * Hkv) * D,
-              "qkv buffer too small");
+  TORCH_CHECK(hq >= 1 && qkv.size(0) == B &&
+              qkv_row >= (hq + 2 * Hkv) * D, "qkv buffer too small");
+  TORCH_CHECK(D % 2 == 0 && D / 2 <= 1024, "bad head dim");
+  TORCH_CHECK(positions.numel() == B, "positions size mismatch");
+  TORCH_CHECK(cos_sin.dim() == 3 && cos_sin.size(1) == D / 2 &&
+              cos_sin.size(2) == 2, "cos_sin must be [max_pos, D/2, 2]");
+  TORCH_CHECK(ksplit >= 1, "ksplit must be at least 1");
   TORCH_CHECK(slabs.numel() >= (int64_t)ksplit * B * qkv_row,
               "slabs too small");
   launch_rope_kv_slab(qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(),
@@ -302,6 +316,9 @@ void attn_decode(torch::Tensor o, torch::Tensor q, torch::Tensor kc,
   TORCH_CHECK(Hq % Hkv == 0 && Hq / Hkv <= 8,
               "grouped heads per kv head must divide and be <= 8");
   TORCH_CHECK(kc.size(0) == B && kc.size(3) == D, "kc shape mismatch");
+  TORCH_CHECK(vc.sizes() == kc.sizes(), "vc shape must equal kc shape");
+  TORCH_CHECK(seq_lens.numel() == B, "seq_lens must hold B entries");
+  TORCH_CHECK(nsplit >= 1 && nsplit <= 1024, "bad nsplit");
   float* ws = nullptr;
   if (nsplit > 1) {
     TORCH_CHECK(partial_ws.has_value(), "nsplit>1 needs partial_ws");
