@@ -22,7 +22,8 @@ def main():
     model = "llama-3-8b" if torch.cuda.is_available() else "tiny"
     fn = mlrun_amd.new_function(name="llm-serving", kind="serving")
     # continuous batching: requests admit at token boundaries;
-    # weight_dtype="fp8w" / kv_dtype="fp8" / replicas=N stack on top,
+    # weight_dtype="fp8w" or "mxfp4w" / kv_dtype="fp8" / replicas=N stack
+    # on top,
     # and fn.deploy(workers=N) scales across processes
     fn.add_model("llama", class_name=LlamaServer, config=model,
                  batch_size=8, max_new_tokens=16,

@@ -478,7 +478,8 @@ class LlamaDecodeEngine:
         # split-K scratch: ksplit * B * N f32 for the largest case
         gemm_shapes = [(qkv_n, h), (h, w.hq * d), (2 * w.inter, h),
                        (h, w.inter), (cfg.vocab_size, h)]
-        scratch = max(ops.pick_gemm_plan(B, n, k)[0] * n
+        scratch = max(max(ops.pick_gemm_plan(B, n, k)[0],
+                          ops.pick_mxfp4_ksplit(B, n, k)) * n
                       for n, k in gemm_shapes)
         self.buf_tokens = torch.zeros(B, dtype=torch.int64,
                                       device=self.device)
@@ -514,6 +515,11 @@ class LlamaDecodeEngine:
             self.buf_h8_scale = torch.empty(B, dtype=torch.float32,
                                             device=self.device)
             self.rebuild_fp8_packs()
+        # opt-in mxfp4-weight decode (W4A16): OCP MXFP4 packs keyed the
+        # same way; activations stay bf16, so no sidecars exist here
+        self._mx4_packs = {}
+        if weight_dtype == "mxfp4w":
+            self.rebuild_weight_packs()
         # fill-based (ns4 at B=32): the graph bakes ONE nsplit for all
         # context lengths, and decode mostly runs at S << max_seq_len —
         # measured (scripts/bench_attn_longctx.py): chunk-aware ns16
@@ -766,8 +772,14 @@ class LlamaDecodeEngine:
 
     def _gemm(self, a, w_, out, a8=None, a_scale=None):
         """skinny GEMM into a preallocated bf16 out + f32 scratch.
-        Uses the fp8-weight pack when this engine runs in fp8w mode;
-        a8/a_scale skip the quant launch (rmsnorm sidecar)."""
+        Uses the mxfp4 / fp8 weight pack when this engine runs in
+        mxfp4w / fp8w mode; a8/a_scale skip the fp8 quant launch
+        (rmsnorm sidecar)."""
+        pack = self._mx4_packs.get(id(w_))
+        if pack is not None:
+            ksplit = ops.pick_mxfp4_ksplit(self.B, *w_.shape)
+            return ops.skinny_gemm_mxfp4(a, pack[0], pack[1], out=out,
+                                         c_f32=self.buf_c32, ksplit=ksplit)
         pack = self._fp8_packs.get(id(w_))
         if pack is not None:
             M, K = a.shape
@@ -933,7 +945,9 @@ class LlamaDecodeEngine:
         on = self.on_gpu and self.tp_size == 1 and mode != "none"
         use_slabs = on and self.weight_dtype == "bf16" and \
             self.kv_dtype == "bf16"  # qkv slab (bf16 caches only)
-        use_norm_slabs = on and mode == "all" 
+        # (the slab GEMM reads the bf16 masters: never under mxfp4w)
+        use_norm_slabs = on and mode == "all" and \
+            self.weight_dtype != "mxfp4w"
         lora = self.lora is not None
         if lora:
             # the adapter delta has to land on the bf16 GEMM output
@@ -1161,6 +1175,23 @@ class LlamaDecodeEngine:
                     ops.quantize_fp8_weight(layer[key])
         self._fp8_packs[id(w.lm_head)] = \
             ops.quantize_fp8_weight(w.lm_head)
+
+    def rebuild_weight_packs(self):
+        """(Re)quantize the packs of the engine's weight mode (fp8w or
+        mxfp4w) from the CURRENT weights; a no-op for bf16 and for
+        engines that run the bf16 masters (CPU, tensor parallel)."""
+        self.rebuild_fp8_packs()
+        if self.weight_dtype != "mxfp4w" or not (self.on_gpu and
+                                                 self.tp_size == 1):
+            return
+        w = self.weights
+        self._mx4_packs = {}
+        for layer in w.layers:
+            for key in ("wqkv", "wo", "wgu", "wdown"):
+                self._mx4_packs[id(layer[key])] = \
+                    ops.quantize_mxfp4_weight(layer[key])
+        self._mx4_packs[id(w.lm_head)] = \
+            ops.quantize_mxfp4_weight(w.lm_head)
 
     def _kscale(self, li):
         return None if self.k_scale is None else self.k_scale[li]
@@ -1943,6 +1974,10 @@ class LlamaServer:
             raise ValueError(
                 f'speculative={k} conflicts with weight_dtype="fp8w": '
                 "the verify pass runs on the bf16 weights")
+        if self.weight_dtype == "mxfp4w":
+            raise ValueError(
+                f'speculative={k} conflicts with weight_dtype="mxfp4w": '
+                "the verify pass runs on the bf16 weights")
 
     def post_init(self, mode="sync"):
         stream = getattr(self.context, "stream", None) if self.context \
@@ -2011,6 +2046,7 @@ class LlamaServer:
                 prefix_cache_blocks=self.prefix_cache_blocks)
             replica.weight_dtype = first.weight_dtype
             replica._fp8_packs = first._fp8_packs  # shared packs
+            replica._mx4_packs = first._mx4_packs
             if first.weight_dtype == "fp8w" and replica.on_gpu:
                 import torch as _torch
 
@@ -2029,10 +2065,11 @@ class LlamaServer:
             state = torch.load(model_file, map_location=first.device,
                                weights_only=True)
             first.weights.load_state_dict(state)
-            first.rebuild_fp8_packs()  # packs quantized pre-load are
-            self.model_spec = spec     # stale (fp8w + model_path)
+            first.rebuild_weight_packs()  # packs quantized pre-load
+            self.model_spec = spec  # are stale (fp8w/mxfp4w + model_path)
             for replica in self.engines[1:]:
                 replica._fp8_packs = first._fp8_packs
+                replica._mx4_packs = first._mx4_packs
         # adapters go into the shared table slots before any capture
         for name, path in self.adapters.items():
             from ..artifacts import get_model

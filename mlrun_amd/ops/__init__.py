@@ -187,6 +187,13 @@ _GEMM_PLAN_TABLE = {
     (128256, 4096): (1, 0),   # lm_head
 }
 
+# mxfp4w keeps the table's ksplit except where another split measured
+# clearly better IN THE DECODE STEP (scripts/bench_gemm_mxfp4.py, batch
+# 32, context 160, two alternating runs each): qkv 4 -> 1 and down 4 -> 2
+# together take the step from 4602 / 4595 us to 4450 / 4452 us (-3.2%,
+# min-max spreads of 5..18 us); alone the kernels gain 14% and 11%.
+_MXFP4_KSPLIT = {(6144, 4096): 1, (4096, 14336): 2}
+
 # e2e A/B override: MLRUN_GEMM_PLAN="6144x4096=2,2;4096x4096=4,2"
 _plan_env = os.environ.get("MLRUN_GEMM_PLAN", "")
 if _plan_env:
@@ -195,6 +202,7 @@ if _plan_env:
         _n, _k = _shape.split("x")
         _ks, _var = _plan.split(",")
         _GEMM_PLAN_TABLE[(int(_n), int(_k))] = (int(_ks), int(_var))
+        _MXFP4_KSPLIT.pop((int(_n), int(_k)), None)  # the override wins
 
 
 def pick_gemm_plan(M: int, N: int, K: int) -> tuple:
@@ -209,6 +217,12 @@ def pick_gemm_plan(M: int, N: int, K: int) -> tuple:
         ksplit = max(1, min(1024 // nblocks_ws, K // 1024, 8))
         return ksplit, 1
     return pick_ksplit(M, N, K), 0
+
+
+def pick_mxfp4_ksplit(M: int, N: int, K: int) -> int:
+    """ksplit of the mxfp4w decode GEMM: its own measured entries, else
+    the bf16 plan's."""
+    return _MXFP4_KSPLIT.get((N, K)) or pick_gemm_plan(M, N, K)[0]
 
 
 def skinny_gemm(a: torch.Tensor, w: torch.Tensor,
@@ -332,6 +346,149 @@ def skinny_gemm_fp8(a8: torch.Tensor, a_scale: torch.Tensor,
     w = _fp8_pair_unswizzle(w8).view(torch.float8_e4m3fn).float() * \
         w_scale[:, None].float()
     result = (a @ w.t()).to(torch.bfloat16)
+    if out is not None:
+        out.copy_(result)
+        return out
+    return result
+
+
+# OCP MXFP4: e2m1 magnitudes by 3-bit code (the sign sits in bit 3), one
+# E8M0 power-of-two scale per 32 values along K
+_MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# midpoints between neighbouring magnitudes; True where the tie goes UP
+# to the even code
+_MXFP4_MID = ((0.25, False), (0.75, True), (1.25, False), (1.75, True),
+              (2.5, False), (3.5, True), (5.0, False))
+
+
+def _mxfp4_scale_order(nblk: int, device) -> torch.Tensor:
+    """Physical order of a row's scale bytes: phys[p] = logical[order[p]].
+    A 128-k super-step has 4 blocks (one per lane group g); super-steps
+    come in groups of four stored [g][step], so the kernel finds a lane
+    group's four scales in one dword.  The K/128 % 4 super-steps after
+    the last full group keep the natural [step][g] order."""
+    order = torch.arange(nblk, device=device)
+    full = nblk // 16 * 16
+    order[:full] = order[:full].view(-1, 4, 4).transpose(1, 2).reshape(-1)
+    return order
+
+
+def _check_mxfp4_k(k: int):
+    if k < 128 or k % 128 != 0:
+        raise ValueError(f"mxfp4 needs K % 128 == 0 and K >= 128, got K={k}")
+
+
+def quantize_mxfp4_weight(w: torch.Tensor):
+    """bf16 [N, K] -> (w4 uint8 [N, K/2], w_scale uint8 [N, K/32]) in
+    OCP MXFP4: per block of 32 consecutive k the shared exponent is
+    floor(log2(amax)) - 2 clamped to [-120, 120] (0 for an all-zero
+    block), elements round to the nearest e2m1 value with ties to the
+    even code and saturate at 6.  Two codes per byte, even k in the low
+    nibble; the scale bytes (e + 127) sit in the kernel's grouped order.
+    Runs once per weight, off the hot path."""
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise ValueError("w must be a bf16 [N, K] tensor, got "
+                         f"{w.dtype} {tuple(w.shape)}")
+    n, k = w.shape
+    _check_mxfp4_k(k)
+    x = w.float().view(n, k // 32, 32)
+    amax = x.abs().amax(dim=-1)
+    # amax = m * 2^ex with m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = (torch.frexp(amax)[1] - 3).clamp(-120, 120)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    mag = torch.ldexp(x.abs(), -e[..., None])  # exact: a power of two
+    code = torch.zeros_like(mag, dtype=torch.uint8)
+    for mid, up in _MXFP4_MID:
+        code += (mag >= mid) if up else (mag > mid)
+    code |= ((x < 0) & (code > 0)).to(torch.uint8) << 3
+    code = code.view(n, k // 2, 2)
+    w4 = code[..., 0] | (code[..., 1] << 4)
+    scale = (e + 127).to(torch.uint8)
+    scale = scale[:, _mxfp4_scale_order(k // 32, w.device)]
+    return w4.contiguous(), scale.contiguous()
+
+
+def dequantize_mxfp4_weight(w4: torch.Tensor,
+                            w_scale: torch.Tensor) -> torch.Tensor:
+    """Inverse of quantize_mxfp4_weight: bf16 [N, K] (every scaled e2m1
+    value is exactly a bf16 value)."""
+    if w4.dim() != 2 or w_scale.dim() != 2 or w4.dtype != torch.uint8 or \
+            w_scale.dtype != torch.uint8:
+        raise ValueError("w4 and w_scale must be 2-d uint8 tensors")
+    n, k = w4.shape[0], w4.shape[1] * 2
+    _check_mxfp4_k(k)
+    if tuple(w_scale.shape) != (n, k // 32):
+        raise ValueError(f"w_scale must be [{n}, {k // 32}], got "
+                         f"{tuple(w_scale.shape)}")
+    code = torch.stack([w4 & 0xF, w4 >> 4], dim=-1).view(n, k).long()
+    grid = torch.tensor(_MXFP4_GRID + tuple(-v for v in _MXFP4_GRID),
+                        dtype=torch.float32, device=w4.device)
+    inverse = torch.empty_like(_mxfp4_scale_order(k // 32, w4.device))
+    inverse[_mxfp4_scale_order(k // 32, w4.device)] = \
+        torch.arange(k // 32, device=w4.device)
+    e = w_scale[:, inverse].to(torch.int32) - 127
+    vals = torch.ldexp(grid[code].view(n, k // 32, 32), e[..., None])
+    return vals.view(n, k).to(torch.bfloat16)
+
+
+def skinny_gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor,
+                      w_scale: torch.Tensor, out: torch.Tensor = None,
+                      c_f32: torch.Tensor = None,
+                      ksplit: int = 1) -> torch.Tensor:
+    """out[M,N] = a[M,K] @ dequant(w4, w_scale)^T with bf16 a / out and
+    M <= 64: the weight-only MXFP4 decode GEMM.  On GPU the codes expand
+    to bf16 MFMA fragments in registers; split-K (ksplit > 1) writes f32
+    slabs into c_f32 and a reduce kernel folds them (deterministic, no
+    atomics).  With out and c_f32 given nothing is allocated."""
+    global _EMPTY_F32
+
+    for name, t, dtype in (("a", a, torch.bfloat16), ("w4", w4, torch.uint8),
+                           ("w_scale", w_scale, torch.uint8)):
+        if t.dim() != 2 or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 2-d {dtype} "
+                             f"tensor, got {t.dtype} {tuple(t.shape)}")
+        if t.device != a.device:
+            raise ValueError(f"{name} is on {t.device}, a on {a.device}")
+    M, K = a.shape
+    N = w4.shape[0]
+    _check_mxfp4_k(K)
+    if not 1 <= M <= 64 or N < 1:
+        raise ValueError(f"mxfp4 GEMM needs 1 <= M <= 64, got M={M}, N={N}")
+    if w4.shape[1] != K // 2 or tuple(w_scale.shape) != (N, K // 32):
+        raise ValueError(
+            f"a is [{M}, {K}]: w4 must be [N, {K // 2}] and w_scale "
+            f"[N, {K // 32}], got {tuple(w4.shape)} / {tuple(w_scale.shape)}")
+    # beyond 128 chunks the 128-k rounding of a chunk can drop K's tail
+    if not isinstance(ksplit, int) or not 1 <= ksplit <= 128:
+        raise ValueError(f"ksplit must be an int in [1, 128], got {ksplit!r}")
+    if out is not None and (
+            out.dtype != torch.bfloat16 or out.device != a.device or
+            not out.is_contiguous() or tuple(out.shape) != (M, N)):
+        raise ValueError(f"out must be a contiguous bf16 [{M}, {N}] tensor "
+                         f"on {a.device}")
+    if c_f32 is not None and ksplit > 1 and (
+            c_f32.dtype != torch.float32 or c_f32.device != a.device or
+            not c_f32.is_contiguous() or c_f32.numel() < ksplit * M * N):
+        raise ValueError(f"c_f32 must be contiguous f32 scratch of at least "
+                         f"ksplit*M*N = {ksplit * M * N} elements")
+    if a.is_cuda:
+        ops = _require_hip()
+        if a.data_ptr() % 16 or w4.data_ptr() % 16:
+            raise ValueError("a and w4 must be 16-byte aligned")
+        if out is None:
+            out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
+        if ksplit > 1 and c_f32 is None:
+            c_f32 = torch.empty(ksplit * M * N, dtype=torch.float32,
+                                device=a.device)
+        if c_f32 is None:
+            if _EMPTY_F32 is None or _EMPTY_F32.device != a.device:
+                _EMPTY_F32 = torch.empty(1, dtype=torch.float32,
+                                         device=a.device)
+            c_f32 = _EMPTY_F32
+        ops.skinny_gemm_mxfp4(out, c_f32, a, w4, w_scale, ksplit)
+        return out
+    w = dequantize_mxfp4_weight(w4, w_scale)
+    result = (a.float() @ w.float().t()).to(torch.bfloat16)
     if out is not None:
         out.copy_(result)
         return out

@@ -268,6 +268,37 @@ void skinny_gemm_fp8(torch::Tensor out_bf16, torch::Tensor part_f32,
                          stream());
 }
 
+void skinny_gemm_mxfp4(torch::Tensor out_bf16, torch::Tensor part_f32,
+                       torch::Tensor a, torch::Tensor w4,
+                       torch::Tensor w_scale, int64_t ksplit) {
+  CHECK_DEV(out_bf16); CHECK_CONTIG(out_bf16); CHECK_BF16(out_bf16);
+  CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
+  CHECK_DEV(w4); CHECK_CONTIG(w4); CHECK_U8(w4);
+  CHECK_DEV(w_scale); CHECK_CONTIG(w_scale); CHECK_U8(w_scale);
+  TORCH_CHECK(a.dim() == 2 && w4.dim() == 2 && w_scale.dim() == 2,
+              "a, w4 and w_scale must be 2-d");
+  int64_t M = a.size(0), K = a.size(1), N = w4.size(0);
+  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && K >= 128 && K % 128 == 0,
+              "mxfp4 path needs 1 <= M <= 64 and K % 128 == 0");
+  TORCH_CHECK(w4.size(1) == K / 2 && w_scale.size(0) == N &&
+              w_scale.size(1) == K / 32, "w4 / w_scale shape mismatch");
+  TORCH_CHECK(out_bf16.numel() >= M * N, "out too small");
+  TORCH_CHECK(ksplit >= 1 && ksplit <= 128 && ksplit * M * N <= INT_MAX,
+              "ksplit out of range [1, 128]");
+  TORCH_CHECK((uintptr_t)a.data_ptr() % 16 == 0 &&
+              (uintptr_t)w4.data_ptr() % 16 == 0,
+              "a and w4 must be 16-byte aligned");
+  if (ksplit > 1) {
+    CHECK_DEV(part_f32); CHECK_CONTIG(part_f32); CHECK_F32(part_f32);
+    TORCH_CHECK(part_f32.numel() >= ksplit * M * N,
+                "part_f32 scratch too small");
+  }
+  launch_skinny_gemm_mxfp4(out_bf16.data_ptr(),
+                           ksplit > 1 ? part_f32.data_ptr() : nullptr,
+                           a.data_ptr(), w4.data_ptr(), w_scale.data_ptr(),
+                           (int)M, (int)N, (int)K, (int)ksplit, stream());
+}
+
 void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
                     torch::Tensor a) {
   CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
@@ -842,6 +873,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cast_f32_bf16", &cast_f32_bf16, "f32 -> bf16 cast");
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8,
         "fp8-weight decode GEMM (e4m3, per-row scales)");
+  m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4,
+        "mxfp4-weight decode GEMM (e2m1 codes, E8M0 block scales, bf16 A)");
   m.def("quant_fp8_rows", &quant_fp8_rows,
         "dynamic per-row bf16 -> fp8 e4m3 quantization");
   m.def("attn_decode", &attn_decode, py::arg("o"), py::arg("q"),

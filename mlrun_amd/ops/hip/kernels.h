@@ -60,6 +60,12 @@ void launch_skinny_gemm_fp8(void* out_bf16, void* part_f32, const void* A8,
                             const void* w_scale, int M, int N, int K,
                             int ksplit, void* stream);
 
+// out[M,N] = A[M,K] (bf16) @ dequant(W4 [N,K/2] e2m1 pairs, w_scale
+// [N,K/32] E8M0 in the kernel's grouped order)^T; M <= 64, K % 128 == 0
+void launch_skinny_gemm_mxfp4(void* out_bf16, void* part_f32, const void* A,
+                              const void* W4, const void* w_scale, int M,
+                              int N, int K, int ksplit, void* stream);
+
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
                            int cols, void* stream);
 

@@ -1148,6 +1148,227 @@ void launch_skinny_gemm_fp8(void* out_bf16, void* part_f32, const void* A8,
   }
 }
 
+// ---------------------------------------------------------------------
+// MXFP4 weight-only decode GEMM (W4A16) — the opt-in mxfp4w mode.
+// Weights are OCP microscaling fp4: e2m1 codes, two per byte (even k
+// in the low nibble), one E8M0 power-of-two scale per 32 k.  A scaled
+// e2m1 value IS a bf16 value and its product with a bf16 activation is
+// exact in f32, so the kernel adds no quantization of its own: the
+// codes expand to bf16 B fragments in registers
+// (v_cvt_scalef32_pk_bf16_fp4) and feed the bf16 MFMA against the
+// PLAIN bf16 activation rows.
+//
+// Unit of the K loop: a 128-k super-step.  Lane group g = lane >> 4
+// owns MX block g of it (32 consecutive k, one scale): ONE 16-byte
+// load per weight row brings its 32 codes, dword j of which becomes
+// the B fragment of MFMA j.  The k order inside an MFMA is free as
+// long as A agrees, so MFMA j takes A from k0 + 32 g + 8 j: the four
+// A loads of a lane cover 64 contiguous bytes of the activation row.
+// Per 128 k that is 2 weight loads (bf16: 8, fp8 pair-swizzle: 4).
+//
+// Scale bytes [N, K/32]: super-steps come in groups of four; inside a
+// group the 16 bytes are stored [g][step], so the dword at 4 g holds
+// lane group g's scales of four consecutive super-steps and one dword
+// load serves a whole unrolled body.  The K/128 % 4 super-steps after
+// the last full group keep the natural [step][g] order and take the
+// byte path, as do the steps a wave needs to reach an aligned body.
+//
+// Wave-split structure, comb fold and split-K slabs mirror
+// skinny_gemm_fp8_kernel; chunk and wave ranges are 128-k aligned.
+// ---------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4v;
+
+// 8 e2m1 codes (one dword, low nibble first) x 2^e -> one bf16x8 fragment
+DEV short8v mx4_frag(unsigned int codes, float scale) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+  union { bf16x2v p[4]; short8v v; } f;
+  f.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 0);
+  f.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 1);
+  f.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 2);
+  f.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3);
+  return f.v;
+#else
+  (void)codes;
+  (void)scale;
+  return short8v{};
+#endif
+}
+
+// E8M0 byte `idx` of `packed` as the f32 power of two it encodes
+DEV float mx4_scale(unsigned int packed, int idx) {
+  union { uint32_t i; float f; } v;
+  v.i = ((packed >> (8 * idx)) & 0xffu) << 23;
+  return v.f;
+}
+
+// U super-steps from k; byte sidx + u of sc0 / sc1 scales super-step u
+// of weight row 0 / 1.  All loads are issued, behind the scales that
+// the first convert waits for, before any convert.
+template <int MT, int U>
+DEV void mx4_steps(f32x4v* acc0, f32x4v* acc1,
+                   const unsigned short* const* aptr,
+                   const unsigned char* bptr0, const unsigned char* bptr1,
+                   int k, unsigned int sc0, unsigned int sc1, int sidx) {
+  u32x4v b0[U], b1[U];
+  short8v af[U][MT][4];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    // weights stream through once: non-temporal; A stays cached
+    b0[u] = __builtin_nontemporal_load(
+        reinterpret_cast<const u32x4v*>(bptr0 + (k >> 1) + u * 64));
+    b1[u] = __builtin_nontemporal_load(
+        reinterpret_cast<const u32x4v*>(bptr1 + (k >> 1) + u * 64));
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        af[u][t][j] = *reinterpret_cast<const short8v*>(aptr[t] + k +
+                                                        u * 128 + j * 8);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float s0 = mx4_scale(sc0, sidx + u);
+    const float s1 = mx4_scale(sc1, sidx + u);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const short8v f0 = mx4_frag(b0[u][j], s0);
+      const short8v f1 = mx4_frag(b1[u][j], s1);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[u][t][j], f0,
+                                                          acc0[t], 0, 0, 0);
+        acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[u][t][j], f1,
+                                                          acc1[t], 0, 0, 0);
+      }
+    }
+  }
+}
+
+template <bool SPLIT, int MT>
+__global__ __launch_bounds__(256) void skinny_gemm_mxfp4_kernel(
+    void* __restrict__ out, const unsigned short* __restrict__ A,
+    const unsigned char* __restrict__ W4,
+    const unsigned char* __restrict__ WS, int M, int N, int K, int ksplit) {
+  const int lane = threadIdx.x & 63;
+  // scalar, so that the k range and its loops stay on the scalar unit
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n0 = blockIdx.x * 32;
+  if (n0 >= N) return;
+  int cbegin = 0, cend = K;
+  if (SPLIT) {
+    const int kchunk = (K / ksplit + 127) & ~127;
+    cbegin = min((int)blockIdx.y * kchunk, K);  // short or empty at the end
+    cend = min(cbegin + kchunk, K);
+  }
+  const int per_wave = (((cend - cbegin) / 4) + 127) & ~127;
+  const int kbegin = cbegin + wave * per_wave;  // may lie past cend: empty
+  const int kend = min(kbegin + per_wave, cend);
+
+  const int g = lane >> 4;
+  const int brow0 = min(n0 + (lane & 15), N - 1);
+  const int brow1 = min(n0 + (lane & 15) + 16, N - 1);
+  const int nblk = K >> 5;  // scale bytes per row
+  const unsigned short* aptr[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+    aptr[t] = A + (size_t)min((lane & 15) + 16 * t, M - 1) * K + g * 32;
+  const unsigned char* bptr0 = W4 + (size_t)brow0 * (K >> 1) + g * 16;
+  const unsigned char* bptr1 = W4 + (size_t)brow1 * (K >> 1) + g * 16;
+  const unsigned char* sptr0 = WS + (size_t)brow0 * nblk;
+  const unsigned char* sptr1 = WS + (size_t)brow1 * nblk;
+
+  f32x4v acc0[MT], acc1[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    acc0[t] = {0.f, 0.f, 0.f, 0.f};
+    acc1[t] = {0.f, 0.f, 0.f, 0.f};
+  }
+
+  // byte path: one super-step, its scale byte found in either order
+  const int kgrouped = K & ~511;  // k below this lies in a full group
+  auto single = [&](int k) {
+    const int s = k >> 7;
+    const int off = 16 * (s >> 2) +
+                    (k < kgrouped ? 4 * g + (s & 3) : 4 * (s & 3) + g);
+    const unsigned int sc0 = sptr0[off], sc1 = sptr1[off];
+    __builtin_amdgcn_sched_barrier(0);
+    mx4_steps<MT, 1>(acc0, acc1, aptr, bptr0, bptr1, k, sc0, sc1, 0);
+  };
+
+  constexpr int UNR = (MT == 1) ? 4 : (MT == 2 ? 2 : 1);  // super-steps
+  int k = kbegin;
+  // up to the first body that does not straddle a scale group
+  for (; k < kend && ((k >> 7) & (UNR - 1)); k += 128) single(k);
+  const int kbody = min(kend, kgrouped);
+  for (; k + UNR * 128 <= kbody; k += UNR * 128) {
+    const int s = k >> 7;
+    unsigned int sc0, sc1;  // memcpy: the tensor's base may be unaligned
+    __builtin_memcpy(&sc0, sptr0 + 16 * (s >> 2) + 4 * g, 4);
+    __builtin_memcpy(&sc1, sptr1 + 16 * (s >> 2) + 4 * g, 4);
+    __builtin_amdgcn_sched_barrier(0);
+    mx4_steps<MT, UNR>(acc0, acc1, aptr, bptr0, bptr1, k, sc0, sc1, s & 3);
+  }
+  for (; k < kend; k += 128) single(k);
+
+  __shared__ float comb[4][16 * MT][32];
+  const int crow_base = g * 4;
+  const int ccol = lane & 15;
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      comb[wave][16 * t + crow_base + r][ccol] = acc0[t][r];
+      comb[wave][16 * t + crow_base + r][ccol + 16] = acc1[t][r];
+    }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int c = 0; c < 8 * MT; ++c) {
+      const int cell = lane * 8 * MT + c;
+      const int m = cell >> 5;
+      const int n = cell & 31;
+      if (m >= M || n0 + n >= N) continue;
+      const float sum = ((comb[0][m][n] + comb[1][m][n]) + comb[2][m][n]) +
+                        comb[3][m][n];
+      if (SPLIT) {
+        float* part = (float*)out + (size_t)blockIdx.y * M * N;
+        part[(size_t)m * N + n0 + n] = sum;
+      } else {
+        ((unsigned short*)out)[(size_t)m * N + n0 + n] = f2bf(sum);
+      }
+    }
+  }
+}
+
+template <bool SPLIT>
+static void dispatch_skinny_gemm_mxfp4(void* out, const void* A,
+                                       const void* W4, const void* WS,
+                                       int M, int N, int K, int ksplit,
+                                       void* stream) {
+  auto kern = M > 32   ? skinny_gemm_mxfp4_kernel<SPLIT, 4>
+              : M > 16 ? skinny_gemm_mxfp4_kernel<SPLIT, 2>
+                       : skinny_gemm_mxfp4_kernel<SPLIT, 1>;
+  const dim3 grid((N + 31) / 32, ksplit > 1 ? ksplit : 1);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, out,
+                     (const unsigned short*)A, (const unsigned char*)W4,
+                     (const unsigned char*)WS, M, N, K, ksplit);
+}
+
+void launch_skinny_gemm_mxfp4(void* out_bf16, void* part_f32, const void* A,
+                              const void* W4, const void* w_scale, int M,
+                              int N, int K, int ksplit, void* stream) {
+  if (ksplit <= 1) {
+    dispatch_skinny_gemm_mxfp4<false>(out_bf16, A, W4, w_scale, M, N, K,
+                                      ksplit, stream);
+  } else {
+    dispatch_skinny_gemm_mxfp4<true>(part_f32, A, W4, w_scale, M, N, K,
+                                     ksplit, stream);
+    launch_reduce_cast(out_bf16, part_f32, M, N, ksplit, stream);
+  }
+}
+
 // dynamic per-row fp8 quantization of bf16 activations:
 // a8[r][k] = round(a[r][k] / (amax_r / 448)); a_scale[r] = amax_r / 448
 __global__ void quant_fp8_rows_kernel(unsigned char* __restrict__ a8,
