@@ -106,12 +106,23 @@ class LlamaWeights:
         self.final_norm = torch.ones(h, dtype=torch.bfloat16, device=device)
         self.lm_head = w(cfg.vocab_size, h)
         self.hq, self.hkv, self.inter = hq, hkv, inter
+        # set by LlamaDecodeEngine.release_master_weights(): the bf16
+        # projection weights and lm_head are gone (None), packs serve
+        self.masters_released = False
+
+    def _check_masters(self, what):
+        if self.masters_released:
+            raise ValueError(
+                f"{what}: the bf16 master weights were released "
+                "(release_master_weights()); build a new engine to load "
+                "or save weights")
 
     def load_state_dict(self, state: dict):
         """Load a checkpoint saved by state_dict() — or a TRAINING
         checkpoint (LlamaForCausalLM.state_dict(), keys like
         "embed.weight"/"blocks.N..."), converted in place: artifacts
         logged by LlamaTrainer.save_checkpoint serve directly."""
+        self._check_masters("load_state_dict")
         if "embed" not in state and "embed.weight" in state:
             state = _training_state_to_decode(state)
         self.embed.copy_(state["embed"])
@@ -122,6 +133,7 @@ class LlamaWeights:
         self.lm_head.copy_(state["lm_head"])
 
     def state_dict(self) -> dict:
+        self._check_masters("state_dict")
         out = {"embed": self.embed, "final_norm": self.final_norm,
                "lm_head": self.lm_head}
         for i, layer in enumerate(self.layers):
@@ -283,10 +295,15 @@ class LoraTables:
         self.loaded = set()  # slots holding an adapter
         bf16 = dict(dtype=torch.bfloat16, device=weights.device)
         self.layers = []
-        for layer in weights.layers:
+        # [N, K] of every projection, kept here: the masters may be
+        # released while adapters still load
+        self.shapes = [{proj: tuple(layer[proj].shape)
+                        for proj in LORA_PROJECTIONS}
+                       for layer in weights.layers]
+        for shapes in self.shapes:
             tables = {}
             for proj in LORA_PROJECTIONS:
-                n, k = layer[proj].shape
+                n, k = shapes[proj]
                 tables[proj] = (
                     torch.zeros(self.max_adapters, self.rank, k, **bf16),
                     torch.zeros(self.max_adapters, n, self.rank, **bf16))
@@ -332,7 +349,7 @@ class LoraTables:
                 if key not in state:
                     raise ValueError(f"adapter state lacks {key!r}")
             mat_a, mat_b = state[key_a], state[key_b]
-            n, k = self.weights.layers[li][proj].shape
+            n, k = self.shapes[li][proj]
             if mat_a.dim() != 2 or mat_a.shape[1] != k:
                 raise ValueError(f"{key_a}: expected [r, {k}], got "
                                  f"{tuple(mat_a.shape)}")
@@ -355,6 +372,36 @@ class LoraTables:
         self.loaded.add(slot)
 
 
+MX4_PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
+
+
+class _Mx4Packs(dict):
+    """The mxfp4 packs of an engine: (w4, w_scale) keyed by (layer index,
+    projection name) and by "lm_head", so that they outlive the masters
+    (the id of a freed tensor can be reused).  The engine itself looks
+    packs up by these names only (``dict.get`` does not reach
+    ``__missing__``).  ``packs[id(master)]``, the key from before the
+    packs had names, still resolves while that master is resident; it is
+    kept for callers written against the old key, tests among them, and
+    scans the layers, so it is not for a hot path."""
+
+    def __init__(self, weights: "LlamaWeights" = None):
+        super().__init__()
+        self.weights = weights
+
+    def __missing__(self, key):
+        w = self.weights
+        if isinstance(key, int) and w is not None \
+                and not w.masters_released:
+            if id(w.lm_head) == key:
+                return self["lm_head"]
+            for li, layer in enumerate(w.layers):
+                for name in MX4_PROJECTIONS:
+                    if id(layer[name]) == key:
+                        return self[(li, name)]
+        raise KeyError(key)
+
+
 class LlamaDecodeEngine:
     """Batched generation engine: prefill (hipBLASLt+SDPA) + hipGraph-
     captured decode step on the custom kernel chain.
@@ -374,7 +421,21 @@ class LlamaDecodeEngine:
                  max_adapters: int = 0, lora_rank: int = 16,
                  lora: "LoraTables" = None, sampling: str = "engine",
                  logit_processors: bool = False,
-                 prefix_cache_blocks: int = 0):
+                 prefix_cache_blocks: int = 0,
+                 prefill_gemm: str = "library"):
+        if prefill_gemm not in ("library", "mxfp4"):
+            raise ValueError(f"unknown prefill_gemm {prefill_gemm!r} "
+                             "(expected 'library' or 'mxfp4')")
+        device_type = torch.device(
+            device or ("cuda:0" if torch.cuda.is_available() else "cpu")).type
+        if prefill_gemm == "mxfp4" and not (
+                weight_dtype == "mxfp4w" and device_type == "cuda"
+                and tp_size == 1):
+            raise ValueError(
+                f'prefill_gemm="mxfp4" needs weight_dtype="mxfp4w" on one '
+                f"GPU, got weight_dtype={weight_dtype!r} on {device_type} "
+                f"with tp_size={tp_size}: there are no mxfp4 packs to run "
+                "on")
         if sampling not in ("engine", "request"):
             raise ValueError(f"unknown sampling mode {sampling!r} "
                              "(expected 'engine' or 'request')")
@@ -517,9 +578,14 @@ class LlamaDecodeEngine:
             self.rebuild_fp8_packs()
         # opt-in mxfp4-weight decode (W4A16): OCP MXFP4 packs keyed the
         # same way; activations stay bf16, so no sidecars exist here
-        self._mx4_packs = {}
+        self._mx4_packs = _Mx4Packs()
         if weight_dtype == "mxfp4w":
             self.rebuild_weight_packs()
+        # "library": the prefills multiply by the bf16 masters (hipBLASLt);
+        # "mxfp4": they run ops.gemm_mxfp4 on the packs the decode step
+        # reads, so one model serves both phases and the masters can go
+        # (release_master_weights)
+        self.prefill_gemm = prefill_gemm
         # fill-based (ns4 at B=32): the graph bakes ONE nsplit for all
         # context lengths, and decode mostly runs at S << max_seq_len —
         # measured (scripts/bench_attn_longctx.py): chunk-aware ns16
@@ -770,16 +836,24 @@ class LlamaDecodeEngine:
             self._ksplits[key] = ops.pick_gemm_plan(self.B, *key)
         return self._ksplits[key]
 
-    def _gemm(self, a, w_, out, a8=None, a_scale=None):
-        """skinny GEMM into a preallocated bf16 out + f32 scratch.
-        Uses the mxfp4 / fp8 weight pack when this engine runs in
-        mxfp4w / fp8w mode; a8/a_scale skip the fp8 quant launch
-        (rmsnorm sidecar)."""
-        pack = self._mx4_packs.get(id(w_))
+    def _master(self, key):
+        """The bf16 weight named ``key``: (layer index, projection) or
+        "lm_head"."""
+        w = self.weights
+        return w.lm_head if key == "lm_head" else w.layers[key[0]][key[1]]
+
+    def _gemm(self, a, key, out, a8=None, a_scale=None):
+        """skinny GEMM of a with the weight named ``key`` (see _master)
+        into a preallocated bf16 out + f32 scratch.  Uses the mxfp4 /
+        fp8 weight pack when this engine runs in mxfp4w / fp8w mode;
+        a8/a_scale skip the fp8 quant launch (rmsnorm sidecar)."""
+        pack = self._mx4_packs.get(key)
         if pack is not None:
-            ksplit = ops.pick_mxfp4_ksplit(self.B, *w_.shape)
+            ksplit = ops.pick_mxfp4_ksplit(self.B, pack[0].shape[0],
+                                           a.shape[1])
             return ops.skinny_gemm_mxfp4(a, pack[0], pack[1], out=out,
                                          c_f32=self.buf_c32, ksplit=ksplit)
+        w_ = self._master(key)
         pack = self._fp8_packs.get(id(w_))
         if pack is not None:
             M, K = a.shape
@@ -965,7 +1039,7 @@ class LlamaDecodeEngine:
                         self.buf_qkv, self.k_cache[li], self.v_cache[li],
                         self.buf_c32, positions, self.cos_sin, w.hq, done)
             if not done:
-                self._gemm(self.buf_hidden, layer["wqkv"], self.buf_qkv,
+                self._gemm(self.buf_hidden, (li, "wqkv"), self.buf_qkv,
                            a8=h8, a_scale=h8s)
                 if lora:
                     self._lora_decode(li, "wqkv", self.buf_hidden,
@@ -992,7 +1066,7 @@ class LlamaDecodeEngine:
                         self.buf_hidden, self.buf_residual, self.buf_c32,
                         layer["ffn_norm"], done, cfg.rms_eps)
             if not done:
-                self._gemm(self.buf_attn_out, layer["wo"], self.buf_proj)
+                self._gemm(self.buf_attn_out, (li, "wo"), self.buf_proj)
                 if lora:
                     self._lora_decode(li, "wo", self.buf_attn_out,
                                       self.buf_proj)
@@ -1008,7 +1082,7 @@ class LlamaDecodeEngine:
                 if done:
                     _hip_ops.swiglu_slab(self.buf_act, self.buf_c32, done)
             if not done:
-                self._gemm(self.buf_hidden, layer["wgu"], self.buf_gu,
+                self._gemm(self.buf_hidden, (li, "wgu"), self.buf_gu,
                            a8=h8, a_scale=h8s)
                 if lora:
                     self._lora_decode(li, "wgu", self.buf_hidden,
@@ -1024,7 +1098,7 @@ class LlamaDecodeEngine:
                         self.buf_hidden, self.buf_residual, self.buf_c32,
                         next_norm, done, cfg.rms_eps)
             if not done:
-                self._gemm(self.buf_act, layer["wdown"], self.buf_down)
+                self._gemm(self.buf_act, (li, "wdown"), self.buf_down)
                 if lora:
                     self._lora_decode(li, "wdown", self.buf_act,
                                       self.buf_down)
@@ -1033,7 +1107,7 @@ class LlamaDecodeEngine:
                                       residual=self.buf_residual,
                                       eps=cfg.rms_eps, out=self.buf_hidden,
                                       out8=h8, out_scale=h8s)
-        self._gemm(self.buf_hidden, w.lm_head, self.buf_logits,
+        self._gemm(self.buf_hidden, "lm_head", self.buf_logits,
                    a8=h8, a_scale=h8s)
         if self.sampling == "request":
             if self.logit_processors:
@@ -1185,13 +1259,35 @@ class LlamaDecodeEngine:
                                                  self.tp_size == 1):
             return
         w = self.weights
-        self._mx4_packs = {}
+        w._check_masters("rebuild_weight_packs")
+        self._mx4_packs = _Mx4Packs(w)
+        for li, layer in enumerate(w.layers):
+            for name in MX4_PROJECTIONS:
+                self._mx4_packs[(li, name)] = \
+                    ops.quantize_mxfp4_weight(layer[name])
+        self._mx4_packs["lm_head"] = ops.quantize_mxfp4_weight(w.lm_head)
+
+    def release_master_weights(self):
+        """Free the bf16 wqkv / wo / wgu / wdown of every layer and
+        lm_head (embedding and norm weights stay): with
+        ``prefill_gemm="mxfp4"`` prefill and decode both run on the
+        packs, so an mxfp4w engine then holds 4.25 bits per weight.
+        Engines that share these weights and packs (replicas) keep
+        working.  Afterwards rebuild_weight_packs(), weights.state_dict()
+        and weights.load_state_dict() raise ValueError."""
+        if self.prefill_gemm != "mxfp4":
+            raise ValueError(
+                "release_master_weights() needs prefill_gemm=\"mxfp4\", "
+                f"got prefill_gemm={self.prefill_gemm!r}: the library "
+                "prefill reads the bf16 masters")
+        w = self.weights
+        if w.masters_released:
+            return
+        w.masters_released = True
         for layer in w.layers:
-            for key in ("wqkv", "wo", "wgu", "wdown"):
-                self._mx4_packs[id(layer[key])] = \
-                    ops.quantize_mxfp4_weight(layer[key])
-        self._mx4_packs[id(w.lm_head)] = \
-            ops.quantize_mxfp4_weight(w.lm_head)
+            for name in MX4_PROJECTIONS:
+                layer[name] = None
+        w.lm_head = None
 
     def _kscale(self, li):
         return None if self.k_scale is None else self.k_scale[li]
@@ -1242,13 +1338,26 @@ class LlamaDecodeEngine:
 
     def _prefill_project(self, plan):
         """_run_layers' ``project`` of the prefills: the library GEMM
-        plus the LoRA deltas of ``plan``."""
+        on the masters, or ops.gemm_mxfp4 on the packs under
+        ``prefill_gemm="mxfp4"``, plus the LoRA deltas of ``plan``."""
         layers = self.weights.layers
+        if self.prefill_gemm == "mxfp4":
+            def project(li, name, x):
+                return self._lora_prefill(plan, li, name, x, ops.gemm_mxfp4(
+                    x.contiguous(), *self._mx4_packs[(li, name)]))
+            return project
 
         def project(li, name, x):
             return self._lora_prefill(plan, li, name, x,
                                       x @ layers[li][name].t())
         return project
+
+    def _prefill_logits(self, last):
+        """Logits of the prefills' last-token rows ``last`` [n, H]."""
+        if self.prefill_gemm == "mxfp4":
+            return ops.gemm_mxfp4(last.contiguous(),
+                                  *self._mx4_packs["lm_head"])
+        return last @ self.weights.lm_head.t()
 
     def _dense_attend(self, rows, B, S):
         """_run_layers' ``attend`` of the dense prefills: B prompts of S
@@ -1316,7 +1425,7 @@ class LlamaDecodeEngine:
                                   self._dense_attend(slice(None), B, S))
         self.cache_lens.fill_(S)
         last = hidden.view(B, S, -1)[:, -1]
-        logits = last @ w.lm_head.t()
+        logits = self._prefill_logits(last)
         if self.sampling == "request":
             rows = torch.arange(B, device=self.device)
             self._sample_slots(logits, slice(0, B), (
@@ -1365,7 +1474,7 @@ class LlamaDecodeEngine:
                                   self._dense_attend(slots, Bp, S))
         self.cache_lens[slots] = S
         last = hidden.view(Bp, S, -1)[:, -1]
-        logits = last @ w.lm_head.t()
+        logits = self._prefill_logits(last)
         self._first_tokens(logits, slots, (
             slots.repeat_interleave(S), tokens.reshape(-1), None))
         return logits
@@ -1473,7 +1582,7 @@ class LlamaDecodeEngine:
         self.cache_lens[slots_long] = kv_start + (
             cu_seqlens[1:] - cu_seqlens[:-1])
         last = hidden[cu_seqlens[1:].long() - 1]
-        logits = last @ w.lm_head.t()
+        logits = self._prefill_logits(last)
         if whole is not None and self.logit_processors:
             state = torch.tensor(
                 [slot for slot, p in zip(slot_list, whole) for _ in p]
@@ -1826,6 +1935,13 @@ class LlamaServer:
       schedulers and whatever ``prefill`` says.  Each replica has its
       own pool: a prefix cached on one misses on another.  Not with
       ``kv_dtype="fp8"`` or ``speculative > 0``.  Default 0 = off.
+    - ``prefill_gemm``: "library" (default) prefills on the bf16 master
+      weights; "mxfp4" (needs ``weight_dtype="mxfp4w"``) prefills with
+      ``ops.gemm_mxfp4`` on the packs the decode step reads, so prompt
+      and generated tokens come from one model.  ``release_masters=True``
+      (needs ``prefill_gemm="mxfp4"``) then frees the bf16 projection
+      weights and lm_head once the checkpoint is loaded and packed:
+      the deployment holds 4.25 bits per weight.
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -1839,7 +1955,9 @@ class LlamaServer:
                  lora_rank: int = 16, sampling: str = "engine",
                  top_p: float = 1.0, min_p: float = 0.0,
                  logit_processors: bool = False,
-                 prefix_cache_blocks: int = 0, **class_args):
+                 prefix_cache_blocks: int = 0,
+                 prefill_gemm: str = "library",
+                 release_masters: bool = False, **class_args):
         import queue as queue_mod
         import threading
 
@@ -1925,6 +2043,8 @@ class LlamaServer:
                 f"prefix_cache_blocks={prefix_cache_blocks} conflicts with "
                 f"speculative={self.speculative}: the speculative path "
                 "prefills without the cache")
+        self.prefill_gemm = prefill_gemm
+        self.release_masters = bool(release_masters)
         self.replicas = max(int(replicas), 1)
         self.engines: typing.List[LlamaDecodeEngine] = []
         self.batch_window_ms = batch_window_ms
@@ -2016,6 +2136,11 @@ class LlamaServer:
                 'prefill="packed" needs a bf16 KV cache (the packed '
                 'attention kernel does not read fp8 caches): use '
                 'kv_dtype="bf16" or prefill="exact"')
+        if self.release_masters and self.prefill_gemm != "mxfp4":
+            raise ValueError(
+                "release_masters=True needs prefill_gemm=\"mxfp4\", got "
+                f"prefill_gemm={self.prefill_gemm!r}: the library prefill "
+                "reads the bf16 masters")
         if not torch.cuda.is_available():
             self.replicas = 1
         # sampling="request": the engine-wide temperature / top_k stay
@@ -2033,7 +2158,8 @@ class LlamaServer:
                                   lora_rank=self.lora_rank,
                                   sampling=self.sampling,
                                   logit_processors=self.logit_processors,
-                                  prefix_cache_blocks=self.prefix_cache_blocks)
+                                  prefix_cache_blocks=self.prefix_cache_blocks,
+                                  prefill_gemm=self.prefill_gemm)
         self.engines = [first]
         for _ in range(self.replicas - 1):
             replica = LlamaDecodeEngine(
@@ -2045,6 +2171,7 @@ class LlamaServer:
                 logit_processors=self.logit_processors,
                 prefix_cache_blocks=self.prefix_cache_blocks)
             replica.weight_dtype = first.weight_dtype
+            replica.prefill_gemm = first.prefill_gemm
             replica._fp8_packs = first._fp8_packs  # shared packs
             replica._mx4_packs = first._mx4_packs
             if first.weight_dtype == "fp8w" and replica.on_gpu:
@@ -2078,6 +2205,8 @@ class LlamaServer:
             state = torch.load(adapter_file, map_location="cpu",
                                weights_only=True)
             first.load_adapter(self.adapter_slots[name], state)
+        if self.release_masters:    # packs are final: drop the bf16 copies
+            first.release_master_weights()
         for idx, engine in enumerate(self.engines):
             engine._serve_stream = torch.cuda.Stream() \
                 if engine.on_gpu else None

@@ -431,6 +431,36 @@ def dequantize_mxfp4_weight(w4: torch.Tensor,
     return vals.view(n, k).to(torch.bfloat16)
 
 
+def _check_mxfp4_gemm_args(a, w4, w_scale, out):
+    """The argument checks every mxfp4 GEMM entry point shares (dtype,
+    rank, contiguity, device, pack shapes, K rule, out, and on GPU the
+    16-byte alignment); ValueError before any launch.  Returns M, N, K."""
+    for name, t, dtype in (("a", a, torch.bfloat16), ("w4", w4, torch.uint8),
+                           ("w_scale", w_scale, torch.uint8)):
+        if t.dim() != 2 or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 2-d {dtype} "
+                             f"tensor, got {t.dtype} {tuple(t.shape)}")
+        if t.device != a.device:
+            raise ValueError(f"{name} is on {t.device}, a on {a.device}")
+    M, K = a.shape
+    N = w4.shape[0]
+    _check_mxfp4_k(K)
+    if M < 1 or N < 1:
+        raise ValueError(f"mxfp4 GEMM needs M, N >= 1, got M={M}, N={N}")
+    if w4.shape[1] != K // 2 or tuple(w_scale.shape) != (N, K // 32):
+        raise ValueError(
+            f"a is [{M}, {K}]: w4 must be [N, {K // 2}] and w_scale "
+            f"[N, {K // 32}], got {tuple(w4.shape)} / {tuple(w_scale.shape)}")
+    if out is not None and (
+            out.dtype != torch.bfloat16 or out.device != a.device or
+            not out.is_contiguous() or tuple(out.shape) != (M, N)):
+        raise ValueError(f"out must be a contiguous bf16 [{M}, {N}] tensor "
+                         f"on {a.device}")
+    if a.is_cuda and (a.data_ptr() % 16 or w4.data_ptr() % 16):
+        raise ValueError("a and w4 must be 16-byte aligned")
+    return M, N, K
+
+
 def skinny_gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor,
                       w_scale: torch.Tensor, out: torch.Tensor = None,
                       c_f32: torch.Tensor = None,
@@ -442,30 +472,12 @@ def skinny_gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor,
     atomics).  With out and c_f32 given nothing is allocated."""
     global _EMPTY_F32
 
-    for name, t, dtype in (("a", a, torch.bfloat16), ("w4", w4, torch.uint8),
-                           ("w_scale", w_scale, torch.uint8)):
-        if t.dim() != 2 or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous 2-d {dtype} "
-                             f"tensor, got {t.dtype} {tuple(t.shape)}")
-        if t.device != a.device:
-            raise ValueError(f"{name} is on {t.device}, a on {a.device}")
-    M, K = a.shape
-    N = w4.shape[0]
-    _check_mxfp4_k(K)
-    if not 1 <= M <= 64 or N < 1:
+    M, N, K = _check_mxfp4_gemm_args(a, w4, w_scale, out)
+    if M > 64:
         raise ValueError(f"mxfp4 GEMM needs 1 <= M <= 64, got M={M}, N={N}")
-    if w4.shape[1] != K // 2 or tuple(w_scale.shape) != (N, K // 32):
-        raise ValueError(
-            f"a is [{M}, {K}]: w4 must be [N, {K // 2}] and w_scale "
-            f"[N, {K // 32}], got {tuple(w4.shape)} / {tuple(w_scale.shape)}")
     # beyond 128 chunks the 128-k rounding of a chunk can drop K's tail
     if not isinstance(ksplit, int) or not 1 <= ksplit <= 128:
         raise ValueError(f"ksplit must be an int in [1, 128], got {ksplit!r}")
-    if out is not None and (
-            out.dtype != torch.bfloat16 or out.device != a.device or
-            not out.is_contiguous() or tuple(out.shape) != (M, N)):
-        raise ValueError(f"out must be a contiguous bf16 [{M}, {N}] tensor "
-                         f"on {a.device}")
     if c_f32 is not None and ksplit > 1 and (
             c_f32.dtype != torch.float32 or c_f32.device != a.device or
             not c_f32.is_contiguous() or c_f32.numel() < ksplit * M * N):
@@ -473,8 +485,6 @@ def skinny_gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor,
                          f"ksplit*M*N = {ksplit * M * N} elements")
     if a.is_cuda:
         ops = _require_hip()
-        if a.data_ptr() % 16 or w4.data_ptr() % 16:
-            raise ValueError("a and w4 must be 16-byte aligned")
         if out is None:
             out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
         if ksplit > 1 and c_f32 is None:
@@ -487,12 +497,40 @@ def skinny_gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor,
             c_f32 = _EMPTY_F32
         ops.skinny_gemm_mxfp4(out, c_f32, a, w4, w_scale, ksplit)
         return out
+    return _mxfp4_gemm_cpu(a, w4, w_scale, out)
+
+
+def _mxfp4_gemm_cpu(a, w4, w_scale, out):
     w = dequantize_mxfp4_weight(w4, w_scale)
     result = (a.float() @ w.float().t()).to(torch.bfloat16)
     if out is not None:
         out.copy_(result)
         return out
     return result
+
+
+def gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor, w_scale: torch.Tensor,
+               out: torch.Tensor = None) -> torch.Tensor:
+    """out[M,N] = a[M,K] @ dequant(w4, w_scale)^T for ANY M >= 1, bf16 a /
+    out, on the packs of quantize_mxfp4_weight: the entry point of the
+    mxfp4 prefill.  On GPU M <= 64 runs skinny_gemm_mxfp4 at
+    pick_mxfp4_ksplit; larger M runs the output-tile MFMA kernel (128 x
+    128 or 128 x 64 tiles, the launcher's choice), which dequantizes
+    each weight tile once on its way into LDS.  No split-K: one
+    summation order whatever the grid."""
+    M, N, K = _check_mxfp4_gemm_args(a, w4, w_scale, out)
+    if not a.is_cuda:
+        return _mxfp4_gemm_cpu(a, w4, w_scale, out)
+    if M <= 64:
+        return skinny_gemm_mxfp4(a, w4, w_scale, out=out,
+                                 ksplit=pick_mxfp4_ksplit(M, N, K))
+    ops = _require_hip()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
+    elif out.data_ptr() % 16:      # the tile kernel stores 8-byte words
+        raise ValueError("out must be 16-byte aligned")
+    ops.gemm_mxfp4_tile(out, a, w4, w_scale, 0)
+    return out
 
 
 def rope_kv_fused(qkv: torch.Tensor, k_cache: torch.Tensor,

@@ -299,6 +299,35 @@ void skinny_gemm_mxfp4(torch::Tensor out_bf16, torch::Tensor part_f32,
                            (int)M, (int)N, (int)K, (int)ksplit, stream());
 }
 
+// any-M mxfp4 GEMM on output tiles (prefill); bn 0 = the launcher's choice
+void gemm_mxfp4_tile(torch::Tensor out_bf16, torch::Tensor a,
+                     torch::Tensor w4, torch::Tensor w_scale, int64_t bn) {
+  CHECK_DEV(out_bf16); CHECK_CONTIG(out_bf16); CHECK_BF16(out_bf16);
+  CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
+  CHECK_DEV(w4); CHECK_CONTIG(w4); CHECK_U8(w4);
+  CHECK_DEV(w_scale); CHECK_CONTIG(w_scale); CHECK_U8(w_scale);
+  TORCH_CHECK(a.dim() == 2 && w4.dim() == 2 && w_scale.dim() == 2,
+              "a, w4 and w_scale must be 2-d");
+  TORCH_CHECK(a.device() == out_bf16.device() && a.device() == w4.device() &&
+              a.device() == w_scale.device(), "tensors on different devices");
+  int64_t M = a.size(0), K = a.size(1), N = w4.size(0);
+  // grid.y = ceil(M / 128) must stay below 65536
+  TORCH_CHECK(M >= 1 && M <= 128 * 65535 && N >= 1 && N <= INT_MAX - 128 &&
+              K >= 128 && K % 128 == 0 && K <= INT_MAX - 128,
+              "mxfp4 tile path needs M, N >= 1 and K % 128 == 0");
+  TORCH_CHECK(w4.size(1) == K / 2 && w_scale.size(0) == N &&
+              w_scale.size(1) == K / 32, "w4 / w_scale shape mismatch");
+  TORCH_CHECK(out_bf16.numel() >= M * N, "out too small");
+  TORCH_CHECK(bn == 0 || bn == 64 || bn == 128, "bn must be 0, 64 or 128");
+  TORCH_CHECK((uintptr_t)a.data_ptr() % 16 == 0 &&
+              (uintptr_t)w4.data_ptr() % 16 == 0 &&
+              (uintptr_t)out_bf16.data_ptr() % 16 == 0,
+              "a, w4 and out must be 16-byte aligned");
+  launch_gemm_mxfp4_tile(out_bf16.data_ptr(), a.data_ptr(), w4.data_ptr(),
+                         w_scale.data_ptr(), (int)M, (int)N, (int)K, (int)bn,
+                         stream());
+}
+
 void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
                     torch::Tensor a) {
   CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
@@ -875,6 +904,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp8-weight decode GEMM (e4m3, per-row scales)");
   m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4,
         "mxfp4-weight decode GEMM (e2m1 codes, E8M0 block scales, bf16 A)");
+  m.def("gemm_mxfp4_tile", &gemm_mxfp4_tile,
+        "mxfp4-weight GEMM for any M on 128-row output tiles (prefill)");
   m.def("quant_fp8_rows", &quant_fp8_rows,
         "dynamic per-row bf16 -> fp8 e4m3 quantization");
   m.def("attn_decode", &attn_decode, py::arg("o"), py::arg("q"),

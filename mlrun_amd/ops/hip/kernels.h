@@ -66,6 +66,12 @@ void launch_skinny_gemm_mxfp4(void* out_bf16, void* part_f32, const void* A,
                               const void* W4, const void* w_scale, int M,
                               int N, int K, int ksplit, void* stream);
 
+// the same product for ANY M >= 1 on 128 x bn output tiles (prefill);
+// bn = 0 lets the launcher choose between 128 and 64
+void launch_gemm_mxfp4_tile(void* out_bf16, const void* A, const void* W4,
+                            const void* w_scale, int M, int N, int K, int bn,
+                            void* stream);
+
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
                            int cols, void* stream);
 

@@ -1369,6 +1369,229 @@ void launch_skinny_gemm_mxfp4(void* out_bf16, void* part_f32, const void* A,
   }
 }
 
+// ---------------------------------------------------------------------
+// MXFP4 weight-only PREFILL GEMM: C[M, N] = A[M, K] @ dequant(W4, WS)^T
+// for any M, on the packs of the decode kernel above (same code bytes,
+// same grouped scale order).  Hundreds of activation rows make this a
+// compute-shaped GEMM, so the work is split by OUTPUT TILE, not by K:
+//
+//   grid (ceil(N / BN), ceil(M / 128)), 256 threads = 4 waves in a 2 x 2
+//   grid; a wave owns 64 rows x BN/2 columns = 4 x BN/32 accumulators of
+//   v_mfma_f32_16x16x32_bf16.  BN = 128 (64 accumulator registers per
+//   lane), or 64 when 128-wide tiles would leave most CUs without a
+//   workgroup.  No split-K, no atomics: every C element has one writer
+//   and one summation order, whatever the grid.
+//
+// K loop, 128 k per step (one super-step = four MX blocks of a weight
+// row).  Both operands go through LDS:
+//   A   128 rows x 256 B, copied as it lies (8 x 16 B per thread).
+//   W   BN rows; a thread loads 16 B of codes (32 k, ONE MX block) and
+//       that block's scale byte, expands them with mx4_frag to 64 B of
+//       bf16 and writes those.  The conversion is exact and is paid once
+//       per workgroup: each dequantized fragment is then read by two
+//       waves and four M tiles, and the MFMA loop holds nothing but
+//       ds_read_b128 and MFMA.
+// The global loads of step t+1 are issued into registers before the
+// MFMAs of step t and committed to LDS after the barrier (the PfStage
+// issue / commit pattern of attn_prefill); one LDS stage.
+//
+// LDS layout: row-major, natural k order, rows PADDED to 128 + 8 halves
+// (272 B).  Rows then start 4 banks apart, so the sixteen 16 B fragment
+// reads of a lane group (16 rows, one k chunk) cover all 64 banks once.
+// The commit writes are conflict-free too: 16 lanes write one whole A
+// row, or the chunks 4 g + j of four consecutive W rows.  Padding was
+// chosen over an XOR swizzle because it costs 4 KiB of 68 and keeps
+// every address a plain row * MXT_ROW + k.
+//
+// The product runs transposed (MFMA A operand = W rows, B operand =
+// activation rows): a lane then holds four CONSECUTIVE n of one output
+// row and stores them as one 8 B word when N % 4 == 0.
+//
+// Edges: rows >= M and >= N are clamped on load (they repeat the last
+// row, stay inside the tensors) and never stored; a wave whose whole
+// sub-tile lies outside skips its MFMAs.  Capture-safe: no allocation,
+// no sync.
+// ---------------------------------------------------------------------
+#define MXT_BM 128
+#define MXT_ROW (128 + 8)  // halves per LDS row
+// Built with the packed f32 VALU forms (v_pk_add / mul / fma_f32) off:
+// new kernels of this file do not rely on them.  The kernel has no f32
+// vector arithmetic of its own, so this changes no instruction today.  A
+// function inlines only into one with the same target features, so
+// everything the kernel calls that is not always-inline (its staging
+// lambdas, the barrier) carries the attribute too; without that they
+// become real calls and the staged registers go through scratch.  The
+// host pass does not know the feature.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MXT_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define MXT_NO_PK_F32
+#endif
+
+// __syncthreads() for such a kernel
+__device__ MXT_NO_PK_F32 __attribute__((always_inline)) inline void
+mxt_barrier() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#endif
+}
+
+template <int BN>
+__global__ __launch_bounds__(256) MXT_NO_PK_F32 void gemm_mxfp4_tile_kernel(
+    unsigned short* __restrict__ C, const unsigned short* __restrict__ A,
+    const unsigned char* __restrict__ W4,
+    const unsigned char* __restrict__ WS, int M, int N, int K) {
+  constexpr int NI = BN / 32;   // 16-wide n sub-tiles of a wave
+  constexpr int WCH = BN / 64;  // 16 B code chunks of a thread per step
+  __shared__ __attribute__((aligned(16)))
+      unsigned short lds[(MXT_BM + BN) * MXT_ROW];
+  unsigned short* abuf = lds;
+  unsigned short* wbuf = lds + MXT_BM * MXT_ROW;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lq = lane & 15;
+  const int lh = lane >> 4;
+  const int m0 = blockIdx.y * MXT_BM;
+  const int n0 = blockIdx.x * BN;
+  const int wm0 = m0 + (wave >> 1) * 64;        // this wave's sub-tile
+  const int wn0 = n0 + (wave & 1) * (BN / 2);
+  const bool active = wm0 < M && wn0 < N;       // wave-uniform
+  const int nblk = K >> 5;        // scale bytes per row
+  const int kgrouped = K & ~511;  // k below this lies in a full group
+
+  // --- staging of one thread: A chunk (tid & 15) of rows (tid >> 4) +
+  // 16 i; MX block wg of W rows (tid >> 2) + 64 i
+  const int wg = tid & 3;
+  const unsigned short* ap[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    ap[i] = A + (size_t)min(m0 + (tid >> 4) + 16 * i, M - 1) * K +
+            (tid & 15) * 8;
+  const unsigned char* wp[WCH];
+  const unsigned char* sp[WCH];
+#pragma unroll
+  for (int i = 0; i < WCH; ++i) {
+    const int row = min(n0 + (tid >> 2) + 64 * i, N - 1);
+    wp[i] = W4 + (size_t)row * (K >> 1) + wg * 16;
+    sp[i] = WS + (size_t)row * nblk;
+  }
+  short8v areg[8];
+  u32x4v wreg[WCH];
+  unsigned int sreg[WCH];
+  auto issue = [&](int k0) MXT_NO_PK_F32 {
+    const int s = k0 >> 7;
+    const int soff = 16 * (s >> 2) +
+                     (k0 < kgrouped ? 4 * wg + (s & 3) : 4 * (s & 3) + wg);
+#pragma unroll
+    for (int i = 0; i < WCH; ++i) {
+      wreg[i] = *reinterpret_cast<const u32x4v*>(wp[i] + (k0 >> 1));
+      sreg[i] = sp[i][soff];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      areg[i] = *reinterpret_cast<const short8v*>(ap[i] + k0);
+  };
+  auto commit = [&]() MXT_NO_PK_F32 {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      *reinterpret_cast<short8v*>(abuf + ((tid >> 4) + 16 * i) * MXT_ROW +
+                                  (tid & 15) * 8) = areg[i];
+#pragma unroll
+    for (int i = 0; i < WCH; ++i) {
+      const float scale = mx4_scale(sreg[i], 0);
+      unsigned short* dst = wbuf + ((tid >> 2) + 64 * i) * MXT_ROW + wg * 32;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        *reinterpret_cast<short8v*>(dst + 8 * j) = mx4_frag(wreg[i][j], scale);
+    }
+  };
+
+  f32x4v acc[4][NI];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < NI; ++i) acc[j][i] = f32x4v{0.f, 0.f, 0.f, 0.f};
+  // fragment rows of this lane: k chunk lh of row lq of each sub-tile
+  const unsigned short* afp =
+      abuf + ((wave >> 1) * 64 + lq) * MXT_ROW + lh * 8;
+  const unsigned short* wfp =
+      wbuf + ((wave & 1) * (BN / 2) + lq) * MXT_ROW + lh * 8;
+
+  issue(0);
+  for (int k0 = 0; k0 < K; k0 += 128) {
+    mxt_barrier();  // everyone is done reading the previous step
+    commit();
+    mxt_barrier();
+    if (k0 + 128 < K) issue(k0 + 128);  // flies under the MFMAs
+    if (!active) continue;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      short8v af[4], wf[NI];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        af[j] = *reinterpret_cast<const short8v*>(afp + 16 * j * MXT_ROW +
+                                                  ks * 32);
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+        wf[i] = *reinterpret_cast<const short8v*>(wfp + 16 * i * MXT_ROW +
+                                                  ks * 32);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+          acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              wf[i], af[j], acc[j][i], 0, 0, 0);
+    }
+  }
+
+  // --- epilogue: acc[j][i][r] = C[wm0 + 16 j + lq][wn0 + 16 i + 4 lh + r]
+  if (!active) return;
+  const bool wide = (N & 3) == 0;  // then n < N means n + 3 < N, 8 B aligned
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int m = wm0 + 16 * j + lq;
+    if (m >= M) continue;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int n = wn0 + 16 * i + 4 * lh;
+      if (n >= N) continue;
+      unsigned short* cp = C + (size_t)m * N + n;
+      if (wide) {
+        ushort4 o;
+        o.x = f2bf(acc[j][i][0]);
+        o.y = f2bf(acc[j][i][1]);
+        o.z = f2bf(acc[j][i][2]);
+        o.w = f2bf(acc[j][i][3]);
+        *reinterpret_cast<ushort4*>(cp) = o;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < N) cp[r] = f2bf(acc[j][i][r]);
+      }
+    }
+  }
+}
+
+// bn: 128 or 64 forces the tile width; 0 picks 64 only while the 64-wide
+// grid still fits the 256 CUs at once (measured: docs/kernels.md; past
+// that the 128-wide tile wins at every shape tried)
+void launch_gemm_mxfp4_tile(void* out_bf16, const void* A, const void* W4,
+                            const void* w_scale, int M, int N, int K, int bn,
+                            void* stream) {
+  const int mtiles = (M + MXT_BM - 1) / MXT_BM;
+  if (bn == 0) bn = (long long)mtiles * ((N + 63) / 64) <= 256 ? 64 : 128;
+  auto kern = bn == 64 ? gemm_mxfp4_tile_kernel<64>
+                       : gemm_mxfp4_tile_kernel<128>;
+  hipLaunchKernelGGL(kern, dim3((N + bn - 1) / bn, mtiles), dim3(256), 0,
+                     (hipStream_t)stream, (unsigned short*)out_bf16,
+                     (const unsigned short*)A, (const unsigned char*)W4,
+                     (const unsigned char*)w_scale, M, N, K);
+}
+
 // dynamic per-row fp8 quantization of bf16 activations:
 // a8[r][k] = round(a[r][k] / (amax_r / 448)); a_scale[r] = amax_r / 448
 __global__ void quant_fp8_rows_kernel(unsigned char* __restrict__ a8,
