@@ -21,6 +21,7 @@ Design (MI355X-first, not a port — the reference has no model code):
 
 import math
 import os
+import threading
 import typing
 from dataclasses import dataclass
 
@@ -402,6 +403,29 @@ class _Mx4Packs(dict):
         raise KeyError(key)
 
 
+_SDPA_WARM = set()
+_SDPA_WARM_LOCK = threading.Lock()
+
+
+def _warm_sdpa(device):
+    """One tiny causal SDPA call per device, under a lock, before any
+    prefill.  The attention library behind torch's SDPA keeps its
+    device -> architecture table in an unlocked static map that the first
+    call on a device inserts into; replica workers that prefill for the
+    first time at the same moment race on that insert (seen as "SDPA
+    only supports ..." errors and as crashes in the first events).  Once
+    the entry exists, later calls only read the map."""
+    key = str(device)
+    with _SDPA_WARM_LOCK:
+        if key in _SDPA_WARM:
+            return
+        q = torch.zeros(1, 1, 16, 128, dtype=torch.bfloat16, device=device)
+        torch.nn.functional.scaled_dot_product_attention(q, q, q,
+                                                         is_causal=True)
+        torch.cuda.synchronize(device)
+        _SDPA_WARM.add(key)
+
+
 class LlamaDecodeEngine:
     """Batched generation engine: prefill (hipBLASLt+SDPA) + hipGraph-
     captured decode step on the custom kernel chain.
@@ -482,6 +506,8 @@ class LlamaDecodeEngine:
         self.tp_rank = tp_rank
         self.tp_size = tp_size
         self.use_graph = use_graph and self.on_gpu
+        if self.on_gpu:
+            _warm_sdpa(self.device)
         # sampling: 0 = greedy argmax; otherwise Gumbel-max over
         # logits/T (graph-safe: torch captures RNG ops so every
         # replay draws fresh noise), optionally top-k restricted.
@@ -1011,10 +1037,12 @@ class LlamaDecodeEngine:
         self.cache_lens.add_(1).clamp_(max=self.cfg.max_seq_len)
         positions = self.buf_positions
         # slab fusion (GPU, TP=1): split-K consumers fold the f32 slabs
-        # directly.  MEASURED: fusing into the 16-row norm kernels is a
+        # directly.  MEASURED: fusing into the 16-row norm kernels was a
         # net loss (consumer grid = B rows is parallelism-starved vs the
         # 2048-block reduce_cast), so only the rope/KV consumer (grid
         # B x heads) fuses by default; override with MLRUN_SLAB_MODE.
+        # (mode "all" also drops the bf16 rounding of the fold, so it
+        # changes the tokens; the bit-exact folds are below.)
         mode = os.environ.get("MLRUN_SLAB_MODE", "rope")
         on = self.on_gpu and self.tp_size == 1 and mode != "none"
         use_slabs = on and self.weight_dtype == "bf16" and \
@@ -1022,13 +1050,37 @@ class LlamaDecodeEngine:
         # (the slab GEMM reads the bf16 masters: never under mxfp4w)
         use_norm_slabs = on and mode == "all" and \
             self.weight_dtype != "mxfp4w"
+        # bit-exact decode fusions (bf16 weights, GPU, TP=1, no LoRA):
+        # MLRUN_DECODE_FUSE is a comma list of
+        #   norm    wo / down: split-K slabs folded inside the residual-
+        #           add + RMSNorm kernel (no reduce_cast launch)
+        #   swiglu  gate|up: SwiGLU in the variant-4 GEMM's epilogue
+        # or "none".  Both round where the unfused kernels round, so the
+        # tokens do not depend on the knob.  MLRUN_SLAB_MODE=all (which
+        # folds unrounded sums) wins over it.
+        fuse = {f.strip() for f in os.environ.get(
+            "MLRUN_DECODE_FUSE", "norm,swiglu").split(",")} - {""}
+        if not fuse <= {"norm", "swiglu", "none"} or \
+                ("none" in fuse and len(fuse) > 1):
+            raise ValueError("MLRUN_DECODE_FUSE must be 'none' or a comma "
+                             f"list of 'norm' and 'swiglu', got {fuse}")
+        exact = self.on_gpu and self.tp_size == 1 and \
+            self.weight_dtype == "bf16" and not use_norm_slabs
+        fold_norm = exact and "norm" in fuse
+        fuse_swiglu = exact and "swiglu" in fuse and 16 < B <= 32
         lora = self.lora is not None
         if lora:
             # the adapter delta has to land on the bf16 GEMM output
             # before rope / norm: the slab-fused consumers are bypassed
-            use_slabs = use_norm_slabs = False
-        if use_slabs or use_norm_slabs:
+            use_slabs = use_norm_slabs = fold_norm = fuse_swiglu = False
+        if use_slabs or use_norm_slabs or fold_norm or fuse_swiglu:
             from mlrun_amd import _hip_ops
+        # the consumer of the wo / down slabs, if any
+        norm_slab = None
+        if use_norm_slabs:
+            norm_slab = _hip_ops.fused_add_rmsnorm_slab
+        elif fold_norm:
+            norm_slab = _hip_ops.fused_add_rmsnorm_fold
         for li, layer in enumerate(w.layers):
             # qkv projection -> rope -> caches
             done = 0
@@ -1059,10 +1111,10 @@ class LlamaDecodeEngine:
                             v_scale=self._vscale(li))
             # attn-out projection -> residual+norm
             done = 0
-            if use_norm_slabs:
+            if norm_slab is not None:
                 done = self._gemm_slabs(self.buf_attn_out, layer["wo"])
                 if done:
-                    _hip_ops.fused_add_rmsnorm_slab(
+                    norm_slab(
                         self.buf_hidden, self.buf_residual, self.buf_c32,
                         layer["ffn_norm"], done, cfg.rms_eps)
             if not done:
@@ -1081,6 +1133,10 @@ class LlamaDecodeEngine:
                 done = self._gemm_slabs(self.buf_hidden, layer["wgu"])
                 if done:
                     _hip_ops.swiglu_slab(self.buf_act, self.buf_c32, done)
+            elif fuse_swiglu and self._plan(layer["wgu"]) == (1, 4):
+                _hip_ops.skinny_gemm_swiglu(self.buf_act, self.buf_hidden,
+                                            layer["wgu"])
+                done = 1
             if not done:
                 self._gemm(self.buf_hidden, (li, "wgu"), self.buf_gu,
                            a8=h8, a_scale=h8s)
@@ -1091,10 +1147,10 @@ class LlamaDecodeEngine:
             next_norm = w.layers[li + 1]["attn_norm"] \
                 if li + 1 < cfg.num_layers else w.final_norm
             done = 0
-            if use_norm_slabs:
+            if norm_slab is not None:
                 done = self._gemm_slabs(self.buf_act, layer["wdown"])
                 if done:
-                    _hip_ops.fused_add_rmsnorm_slab(
+                    norm_slab(
                         self.buf_hidden, self.buf_residual, self.buf_c32,
                         next_norm, done, cfg.rms_eps)
             if not done:

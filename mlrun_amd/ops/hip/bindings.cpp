@@ -165,6 +165,80 @@ void fused_add_rmsnorm_slab(torch::Tensor out, torch::Tensor residual,
                                 (int)ksplit, stream());
 }
 
+// a [rows, cols]-shaped dense GPU tensor of `type`, else ValueError
+static void check_value_tensor(const torch::Tensor& t, const char* name,
+                               torch::ScalarType type, const char* type_name,
+                               int64_t dim) {
+  TORCH_CHECK_VALUE(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK_VALUE(t.scalar_type() == type, name, " must be ", type_name);
+  TORCH_CHECK_VALUE(t.is_contiguous(), name, " not contiguous");
+  TORCH_CHECK_VALUE(t.dim() == dim, name, " must have ", dim, " dimensions");
+}
+
+// reduce_cast + fused_add_rmsnorm in one launch, bit for bit:
+// slabs [ksplit, rows, hidden] f32 (spare capacity allowed), residual
+// [rows, hidden] updated in place, out [rows, hidden].  ValueError on
+// anything else, before any launch.
+void fused_add_rmsnorm_fold(torch::Tensor out, torch::Tensor residual,
+                            torch::Tensor slabs, torch::Tensor weight,
+                            int64_t ksplit, double eps) {
+  check_value_tensor(out, "out", torch::kBFloat16, "bf16", 2);
+  check_value_tensor(residual, "residual", torch::kBFloat16, "bf16", 2);
+  check_value_tensor(slabs, "slabs", torch::kFloat32, "f32", slabs.dim());
+  check_value_tensor(weight, "weight", torch::kBFloat16, "bf16", 1);
+  const int64_t rows = out.size(0), hidden = out.size(1);
+  TORCH_CHECK_VALUE(rows >= 1 && rows <= 64, "rows must be in [1, 64]");
+  TORCH_CHECK_VALUE(hidden >= 8 && hidden % 8 == 0 && hidden <= INT_MAX / 64,
+                    "hidden must be a multiple of 8");
+  TORCH_CHECK_VALUE(ksplit >= 1 && ksplit <= 64,
+                    "ksplit must be in [1, 64]");
+  TORCH_CHECK_VALUE(residual.sizes() == out.sizes(),
+                    "residual size mismatch");
+  TORCH_CHECK_VALUE(weight.numel() == hidden, "weight size mismatch");
+  TORCH_CHECK_VALUE(slabs.numel() >= ksplit * rows * hidden,
+                    "slabs too small");
+  TORCH_CHECK_VALUE(out.get_device() == residual.get_device() &&
+                    out.get_device() == slabs.get_device() &&
+                    out.get_device() == weight.get_device(),
+                    "tensors must share one device");
+  for (const torch::Tensor* t : {&out, &residual, &slabs, &weight})
+    TORCH_CHECK_VALUE(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                      "tensors must be 16-byte aligned");
+  launch_fused_add_rmsnorm_fold(out.data_ptr(), residual.data_ptr(),
+                                slabs.data_ptr(), weight.data_ptr(),
+                                (int)rows, (int)hidden, (float)eps,
+                                (int)ksplit, stream());
+}
+
+// act [M, inter] = silu(a @ wgu[:inter]^T) * (a @ wgu[inter:]^T), bf16:
+// the variant-4 decode GEMM with the SwiGLU epilogue, equal bit for bit
+// to skinny_gemm(variant 4, ksplit 1) + swiglu_fused.  16 < M <= 32.
+void skinny_gemm_swiglu(torch::Tensor act, torch::Tensor a,
+                        torch::Tensor wgu) {
+  check_value_tensor(act, "act", torch::kBFloat16, "bf16", 2);
+  check_value_tensor(a, "a", torch::kBFloat16, "bf16", 2);
+  check_value_tensor(wgu, "wgu", torch::kBFloat16, "bf16", 2);
+  const int64_t M = a.size(0), K = a.size(1), N = wgu.size(0);
+  const int64_t inter = act.size(1);
+  TORCH_CHECK_VALUE(M > 16 && M <= 32,
+                    "skinny_gemm_swiglu needs 16 < M <= 32");
+  TORCH_CHECK_VALUE(wgu.size(1) == K, "K mismatch");
+  TORCH_CHECK_VALUE(K >= 32 && K % 32 == 0 && K <= INT_MAX / 64,
+                    "K must be a multiple of 32");
+  TORCH_CHECK_VALUE(act.size(0) == M, "act rows mismatch");
+  TORCH_CHECK_VALUE(N == 2 * inter, "wgu must have 2 * inter rows");
+  TORCH_CHECK_VALUE(inter >= 8 && inter % 8 == 0 && N <= INT_MAX / 64,
+                    "inter must be a multiple of 8");
+  TORCH_CHECK_VALUE(act.get_device() == a.get_device() &&
+                    act.get_device() == wgu.get_device(),
+                    "tensors must share one device");
+  for (const torch::Tensor* t : {&act, &a, &wgu})
+    TORCH_CHECK_VALUE(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                      "tensors must be 16-byte aligned");
+  launch_skinny_gemm_swiglu(act.data_ptr(), a.data_ptr(), wgu.data_ptr(),
+                            (int)M, (int)inter, (int)K, stream());
+}
+
 void swiglu_slab(torch::Tensor out, torch::Tensor slabs, int64_t ksplit) {
   CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
   CHECK_DEV(slabs); CHECK_CONTIG(slabs); CHECK_F32(slabs);
@@ -897,6 +971,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_add_rmsnorm_slab", &fused_add_rmsnorm_slab,
         "slab-sum + residual add + RMSNorm");
   m.def("swiglu_slab", &swiglu_slab, "slab-sum + SwiGLU");
+  m.def("fused_add_rmsnorm_fold", &fused_add_rmsnorm_fold,
+        "reduce_cast + fused_add_rmsnorm in one launch, bit-identical");
+  m.def("skinny_gemm_swiglu", &skinny_gemm_swiglu,
+        "variant-4 gate|up decode GEMM with the SwiGLU epilogue");
   m.def("rope_kv_slab", &rope_kv_slab,
         "slab-sum + rope(q,k) + KV append");
   m.def("cast_f32_bf16", &cast_f32_bf16, "f32 -> bf16 cast");

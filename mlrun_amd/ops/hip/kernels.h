@@ -35,6 +35,14 @@ void launch_fused_add_rmsnorm_slab(void* out, void* residual,
 void launch_swiglu_slab(void* out, const void* slabs, int rows, int inter,
                         int ksplit, void* stream);
 
+void launch_fused_add_rmsnorm_fold(void* out, void* residual,
+                                   const void* slabs, const void* weight,
+                                   int rows, int hidden, float eps,
+                                   int ksplit, void* stream);
+
+void launch_skinny_gemm_swiglu(void* act_out, const void* A, const void* Wgu,
+                               int M, int inter, int K, void* stream);
+
 void launch_rope_kv_slab(void* qkv, void* Kc, void* Vc, const void* slabs,
                          const void* positions, const void* cos_sin, int B,
                          int Hq, int Hkv, int Smax, int D, int qkv_row,

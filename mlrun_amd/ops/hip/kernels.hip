@@ -35,6 +35,14 @@ typedef __attribute__((ext_vector_type(2))) float f32x2v;
 
 #define DEV __device__ __forceinline__
 
+// An f32 result the optimizer must take as it is: it cannot pair it with
+// a neighbour into a packed f32 VALU op (v_pk_add/mul/fma_f32) or
+// contract it into an fma.  Emits no instruction.
+DEV float nopk(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
 DEV float bf2f(unsigned short u) {
   union { uint32_t i; float f; } v;
   v.i = uint32_t(u) << 16;
@@ -52,6 +60,37 @@ DEV unsigned short f2bf(float f) {
 
 struct ushort8 { unsigned short v[8]; };
 struct ushort2v { unsigned short x, y; };
+
+// The sum of squares of the RMSNorm kernels.  fused_add_rmsnorm_kernel
+// and fused_add_rmsnorm_fold_kernel must agree to the bit, so both take
+// the per-chunk accumulation and the block reduction from here: one
+// expression, one reduction tree, and the product rounded before the
+// add in both (no fma contraction, whatever surrounds the inlined code).
+DEV float norm_sumsq8(float sumsq, const float (&z)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) sumsq += nopk(z[j] * z[j]);
+  return sumsq;
+}
+
+// red: 32 floats of LDS; every thread of the block calls this
+DEV float norm_block_inv(float sumsq, float* red, int tid, int nthreads,
+                         int hidden, float eps) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    sumsq += __shfl_down(sumsq, off, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = sumsq;
+  __syncthreads();
+  if (tid < (nthreads >> 6)) sumsq = red[tid];
+  else sumsq = 0.f;
+  if (tid < 64) {
+#pragma unroll
+    for (int off = 2; off > 0; off >>= 1)
+      sumsq += __shfl_down(sumsq, off, 64);
+  }
+  if (tid == 0) red[0] = sumsq;
+  __syncthreads();
+  return rsqrtf(red[0] / hidden + eps);
+}
 
 // ---------------------------------------------------------------------
 // fused residual-add + RMSNorm (bf16):
@@ -90,26 +129,10 @@ __global__ void fused_add_rmsnorm_kernel(
       }
       *reinterpret_cast<ushort8*>(rr + i) = zv;  // updated residual
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sumsq += z[j] * z[j];
+    sumsq = norm_sumsq8(sumsq, z);
   }
-  // block reduce
   __shared__ float red[32];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    sumsq += __shfl_down(sumsq, off, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = sumsq;
-  __syncthreads();
-  if (tid < (nthreads >> 6)) sumsq = red[tid];
-  else sumsq = 0.f;
-  if (tid < 64) {
-#pragma unroll
-    for (int off = 2; off > 0; off >>= 1)
-      sumsq += __shfl_down(sumsq, off, 64);
-  }
-  if (tid == 0) red[0] = sumsq;
-  __syncthreads();
-  const float inv = rsqrtf(red[0] / hidden + eps);
+  const float inv = norm_block_inv(sumsq, red, tid, nthreads, hidden, eps);
 
   const unsigned short* zsrc = has_residual ? rr : xr;
   float amax = 0.f;
@@ -228,6 +251,14 @@ __global__ void silu_mul_kernel(unsigned short* __restrict__ out,
   }
 }
 
+// silu(g) * u on bf16 values: the one expression of swiglu_fused_kernel
+// and of the decode GEMM's SwiGLU epilogue, which must agree to the bit
+DEV unsigned short swiglu_bf16(unsigned short g, unsigned short u) {
+  float gf = bf2f(g);
+  float s = nopk(gf / nopk(1.f + __expf(-gf)));
+  return f2bf(nopk(s * bf2f(u)));
+}
+
 // SwiGLU over a fused gate|up buffer: gu [rows, 2*inter] ->
 // out [rows, inter] = silu(gu[:, :inter]) * gu[:, inter:]
 __global__ void swiglu_fused_kernel(unsigned short* __restrict__ out,
@@ -245,11 +276,7 @@ __global__ void swiglu_fused_kernel(unsigned short* __restrict__ out,
     ushort8 u = *reinterpret_cast<const ushort8*>(row + inter + c);
     ushort8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float gf = bf2f(g.v[j]);
-      float s = gf / (1.f + __expf(-gf));
-      o.v[j] = f2bf(s * bf2f(u.v[j]));
-    }
+    for (int j = 0; j < 8; ++j) o.v[j] = swiglu_bf16(g.v[j], u.v[j]);
     *reinterpret_cast<ushort8*>(out + (size_t)r * inter + c) = o;
   }
 }
@@ -732,10 +759,18 @@ DEV void wait_vmcnt() {
 
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
-template <bool SPLIT, int STAGE_K, int DEPTH>
+//
+// SWIGLU (non-split only): W is a fused gate|up weight [2*inter, K] and
+// out is act [M, inter] = silu(gate) * up.  A workgroup's 32-row tile is
+// then gate rows g0..g0+15 and up rows inter+g0.., g0 = 16*blockIdx.x:
+// only the source rows change, so every gate / up sum is the number the
+// plain kernel writes, and wave 0 rounds both to bf16 and applies
+// swiglu_bf16, as swiglu_fused_kernel does on the stored intermediate.
+template <bool SPLIT, int STAGE_K, int DEPTH, bool SWIGLU = false>
 __global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
     void* __restrict__ out, const unsigned short* __restrict__ A,
     const unsigned short* __restrict__ W, int M, int N, int K, int ksplit) {
+  static_assert(!(SPLIT && SWIGLU), "the SwiGLU epilogue needs whole sums");
   constexpr int MT = 2, NT = 32;
   constexpr int ROW_B = STAGE_K * 2;       // bytes of one row per stage
   constexpr int OP_B = 32 * ROW_B;         // one operand tile
@@ -752,7 +787,15 @@ __global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n0 = blockIdx.x * NT;
-  if (n0 >= N) return;
+  const int inter = N >> 1;          // SWIGLU only
+  const int g0 = blockIdx.x * 16;    // SWIGLU only
+  if (SWIGLU ? g0 >= inter : n0 >= N) return;
+  // W row behind tile row `row`; rows past the end are clamped
+  auto wrow = [&](int row) {
+    if (!SWIGLU) return min(n0 + row, N - 1);
+    return row < 16 ? min(g0 + row, inter - 1)
+                    : inter + min(g0 + row - 16, inter - 1);
+  };
   int cbegin = 0, cend = K;
   if (SPLIT) {
     const int kchunk = (K / ksplit + 31) & ~31;
@@ -784,7 +827,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
   for (int i = 0; i < NDMA_OP; ++i) {
     const int row = i * RPI + lane / LPR;
     const int chunk = (lane % LPR) ^ lds_ring_swz<STAGE_K>(row);
-    wsrc[i] = W + (size_t)min(n0 + row, N - 1) * K + kbegin + chunk * 8;
+    wsrc[i] = W + (size_t)wrow(row) * K + kbegin + chunk * 8;
     asrc[i] = A + (size_t)min(row, M - 1) * K + kbegin + chunk * 8;
   }
   // fragment read: lane l holds row l&15, source chunk (l>>4) + 4*step
@@ -884,10 +927,8 @@ __global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
     const unsigned short* aptr0 = A + (size_t)min(arow, M - 1) * K + kb;
     const unsigned short* aptr1 =
         A + (size_t)min(arow + 16, M - 1) * K + kb;
-    const unsigned short* bptr0 =
-        W + (size_t)min(n0 + arow, N - 1) * K + kb;
-    const unsigned short* bptr1 =
-        W + (size_t)min(n0 + arow + 16, N - 1) * K + kb;
+    const unsigned short* bptr0 = W + (size_t)wrow(arow) * K + kb;
+    const unsigned short* bptr1 = W + (size_t)wrow(arow + 16) * K + kb;
     for (int k = kbegin + nst * STAGE_K; k < kend; k += 32) {
       short8v bf0 = *reinterpret_cast<const short8v*>(bptr0 + k);
       short8v bf1 = *reinterpret_cast<const short8v*>(bptr1 + k);
@@ -926,6 +967,26 @@ __global__ __launch_bounds__(256) void skinny_gemm_ws_lds_kernel(
         *reinterpret_cast<const comb_t*>(lds_ring + 2 * WAVE_B);
     const comb_t& c3 =
         *reinterpret_cast<const comb_t*>(lds_ring + 3 * WAVE_B);
+    if (SWIGLU) {
+      // lane -> row lane/2, eight output columns: one 16-byte store
+      // (inter % 8 == 0, so the eight are inside the row or all outside)
+      const int m = lane >> 1;
+      const int j0 = (lane & 1) * 8;
+      if (m >= M || g0 + j0 >= inter) return;
+      ushort8 o;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int j = j0 + c;
+        const float gate =
+            nopk(nopk(nopk(c0[m][j] + c1[m][j]) + c2[m][j]) + c3[m][j]);
+        const float up = nopk(nopk(nopk(c0[m][j + 16] + c1[m][j + 16]) +
+                                   c2[m][j + 16]) + c3[m][j + 16]);
+        o.v[c] = swiglu_bf16(f2bf(gate), f2bf(up));
+      }
+      *reinterpret_cast<ushort8*>((unsigned short*)out + (size_t)m * inter +
+                                  g0 + j0) = o;
+      return;
+    }
     constexpr int CPL = 4 * MT * 2;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
@@ -1696,7 +1757,7 @@ constexpr int lds_ring_bytes() {
 
 // The rings need more dynamic LDS than the 64 KiB a kernel gets by
 // default.  The first variant-4 call on a device raises the limit of
-// all six instantiations under a lock, so engine replicas that start
+// all nine instantiations under a lock, so engine replicas that start
 // on several threads at once never change a kernel's attributes while
 // another thread launches it.  This is not a stream operation; the
 // first call is expected outside graph capture (engines warm up
@@ -1716,6 +1777,12 @@ static void lds_ring_allow_all() {
       {skinny_gemm_ws_lds_kernel<true, 64, 3>, lds_ring_bytes<64, 3>()},
       {skinny_gemm_ws_lds_kernel<false, 128, 2>, lds_ring_bytes<128, 2>()},
       {skinny_gemm_ws_lds_kernel<true, 128, 2>, lds_ring_bytes<128, 2>()},
+      {skinny_gemm_ws_lds_kernel<false, 64, 2, true>,
+       lds_ring_bytes<64, 2>()},
+      {skinny_gemm_ws_lds_kernel<false, 64, 3, true>,
+       lds_ring_bytes<64, 3>()},
+      {skinny_gemm_ws_lds_kernel<false, 128, 2, true>,
+       lds_ring_bytes<128, 2>()},
   };
   for (const auto& k : all)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k.kern),
@@ -1797,6 +1864,33 @@ void launch_skinny_gemm(void* out_bf16, void* part_f32, const void* A,
                                stream);
     launch_reduce_cast(out_bf16, part_f32, M, N, ksplit, stream);
   }
+}
+
+// act [M, inter] = silu(A @ Wgu[:inter]^T) * (A @ Wgu[inter:]^T) in one
+// launch: the non-split variant-4 kernel of the selected ring with the
+// SwiGLU epilogue.  16 < M <= 32, inter % 8 == 0, K % 32 == 0 (the
+// binding checks).
+void launch_skinny_gemm_swiglu(void* act_out, const void* A, const void* Wgu,
+                               int M, int inter, int K, void* stream) {
+  lds_ring_allow_all();
+  skinny_gemm_kern_t kern;
+  int lds_bytes;
+  switch (gemm_lds_ring_env()) {
+    case 1:
+      kern = skinny_gemm_ws_lds_kernel<false, 64, 3, true>;
+      lds_bytes = lds_ring_bytes<64, 3>();
+      break;
+    case 2:
+      kern = skinny_gemm_ws_lds_kernel<false, 128, 2, true>;
+      lds_bytes = lds_ring_bytes<128, 2>();
+      break;
+    default:
+      kern = skinny_gemm_ws_lds_kernel<false, 64, 2, true>;
+      lds_bytes = lds_ring_bytes<64, 2>();
+  }
+  hipLaunchKernelGGL(kern, dim3((inter + 15) / 16, 1), dim3(256), lds_bytes,
+                     (hipStream_t)stream, act_out, (const unsigned short*)A,
+                     (const unsigned short*)Wgu, M, 2 * inter, K, 1);
 }
 
 // f32 -> bf16 flat cast (epilogue after k-split accumulate)
@@ -1924,6 +2018,158 @@ void launch_fused_add_rmsnorm_slab(void* out, void* residual,
   int threads = hidden >= 2048 ? 256 : 64;
   hipLaunchKernelGGL(fused_add_rmsnorm_slab_kernel, dim3(rows),
                      dim3(threads), 0, (hipStream_t)stream,
+                     (unsigned short*)out, (unsigned short*)residual,
+                     (const float*)slabs, (const unsigned short*)weight,
+                     hidden, eps, ksplit);
+}
+
+// reduce_cast + fused_add_rmsnorm in one launch, to the bit:
+//   x = bf16(slab0 + slab1 + ...)      reduce_cast_kernel's order
+//   residual <- bf16(x + residual) ; out <- rmsnorm(x + residual) * weight
+// with fused_add_rmsnorm_kernel's thread count, element ownership
+// (thread tid owns the 8-wide chunks tid*8 + k*nthreads*8), per-thread
+// order and reduction (norm_sumsq8 / norm_block_inv).  One owner per
+// element, plain loads and stores.  KS > 0 fixes ksplit at compile time
+// so that a chunk's 2*KS slab loads are all issued before the first add.
+
+// x[j] = slab0[j] + slab1[j] + ...  for 8 consecutive floats at p
+template <int KS>
+DEV void fold_load8(f32x4v (&v)[KS ? KS : 1][2], const float* __restrict__ p,
+                    size_t slab_stride) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    v[s][0] = *reinterpret_cast<const f32x4v*>(p + s * slab_stride);
+    v[s][1] = *reinterpret_cast<const f32x4v*>(p + s * slab_stride + 4);
+  }
+}
+
+template <int KS>
+DEV void fold_sum8(float (&x)[8], const f32x4v (&v)[KS ? KS : 1][2],
+                   const float* __restrict__ p, size_t slab_stride,
+                   int ksplit) {
+  if (KS > 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float sum = v[0][j >> 2][j & 3];
+#pragma unroll
+      for (int s = 1; s < KS; ++s) sum = nopk(sum + v[s][j >> 2][j & 3]);
+      x[j] = sum;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = p[j];
+    for (int s = 1; s < ksplit; ++s) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = nopk(x[j] + p[s * slab_stride + j]);
+    }
+  }
+}
+
+// z = bf2f(bf16(x)) + bf2f(residual); returns sumsq + sum z^2 and the
+// rounded new residual
+DEV float fold_add8(float sumsq, const float (&x)[8], const ushort8& rv,
+                    ushort8& zv) {
+  float z[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    z[j] = nopk(bf2f(f2bf(x[j])) + bf2f(rv.v[j]));
+    zv.v[j] = f2bf(z[j]);
+  }
+  return norm_sumsq8(sumsq, z);
+}
+
+DEV ushort8 norm_scale8(const ushort8& zv, const ushort8& wv, float inv) {
+  ushort8 ov;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    ov.v[j] = f2bf(nopk(nopk(bf2f(zv.v[j]) * inv) * bf2f(wv.v[j])));
+  return ov;
+}
+
+template <int KS>
+__global__ void fused_add_rmsnorm_fold_kernel(
+    unsigned short* __restrict__ out, unsigned short* __restrict__ residual,
+    const float* __restrict__ slabs,
+    const unsigned short* __restrict__ weight, int hidden, float eps,
+    int ksplit) {
+  const int row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int nthreads = blockDim.x;
+  const size_t rowbase = (size_t)row * hidden;
+  const size_t slab_stride = (size_t)gridDim.x * hidden;
+  const float* sr = slabs + rowbase;
+  unsigned short* rr = residual + rowbase;
+  unsigned short* outr = out + rowbase;
+  const int step = nthreads * 8;
+  __shared__ float red[32];
+
+  if (hidden <= 2 * step) {
+    // at most two chunks per thread (hidden 4096): every load goes out
+    // before the first use, and the new residual stays in registers for
+    // the second pass.  A thread without a chunk loads chunk 0 of the
+    // row instead (inside the row, never used), so no load is branched.
+    bool has[2];
+    int at[2];
+    f32x4v v[2][KS ? KS : 1][2];
+    ushort8 rv[2], wv[2], zv[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int i = tid * 8 + c * step;
+      has[c] = i < hidden;
+      at[c] = has[c] ? i : 0;
+      fold_load8<KS>(v[c], sr + at[c], slab_stride);
+      rv[c] = *reinterpret_cast<const ushort8*>(rr + at[c]);
+      wv[c] = *reinterpret_cast<const ushort8*>(weight + at[c]);
+    }
+    float sumsq = 0.f;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (!has[c]) continue;
+      float x[8];
+      fold_sum8<KS>(x, v[c], sr + at[c], slab_stride, ksplit);
+      sumsq = fold_add8(sumsq, x, rv[c], zv[c]);
+      *reinterpret_cast<ushort8*>(rr + at[c]) = zv[c];
+    }
+    const float inv = norm_block_inv(sumsq, red, tid, nthreads, hidden, eps);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      if (has[c])
+        *reinterpret_cast<ushort8*>(outr + at[c]) =
+            norm_scale8(zv[c], wv[c], inv);
+    return;
+  }
+
+  // longer rows: fused_add_rmsnorm_kernel's two passes, the second one
+  // re-reading the residual this thread wrote
+  float sumsq = 0.f;
+  for (int i = tid * 8; i < hidden; i += step) {
+    f32x4v v[KS ? KS : 1][2];
+    fold_load8<KS>(v, sr + i, slab_stride);
+    const ushort8 rv = *reinterpret_cast<const ushort8*>(rr + i);
+    float x[8];
+    fold_sum8<KS>(x, v, sr + i, slab_stride, ksplit);
+    ushort8 zv;
+    sumsq = fold_add8(sumsq, x, rv, zv);
+    *reinterpret_cast<ushort8*>(rr + i) = zv;
+  }
+  const float inv = norm_block_inv(sumsq, red, tid, nthreads, hidden, eps);
+  for (int i = tid * 8; i < hidden; i += step) {
+    const ushort8 zv = *reinterpret_cast<const ushort8*>(rr + i);
+    const ushort8 wv = *reinterpret_cast<const ushort8*>(weight + i);
+    *reinterpret_cast<ushort8*>(outr + i) = norm_scale8(zv, wv, inv);
+  }
+}
+
+void launch_fused_add_rmsnorm_fold(void* out, void* residual,
+                                   const void* slabs, const void* weight,
+                                   int rows, int hidden, float eps,
+                                   int ksplit, void* stream) {
+  const int threads = hidden >= 2048 ? 256 : 64;
+  auto kern = ksplit == 1   ? fused_add_rmsnorm_fold_kernel<1>
+              : ksplit == 2 ? fused_add_rmsnorm_fold_kernel<2>
+              : ksplit == 4 ? fused_add_rmsnorm_fold_kernel<4>
+                            : fused_add_rmsnorm_fold_kernel<0>;
+  hipLaunchKernelGGL(kern, dim3(rows), dim3(threads), 0, (hipStream_t)stream,
                      (unsigned short*)out, (unsigned short*)residual,
                      (const float*)slabs, (const unsigned short*)weight,
                      hidden, eps, ksplit);
