@@ -446,10 +446,14 @@ class LlamaDecodeEngine:
                  lora: "LoraTables" = None, sampling: str = "engine",
                  logit_processors: bool = False,
                  prefix_cache_blocks: int = 0,
-                 prefill_gemm: str = "library"):
+                 prefill_gemm: str = "library",
+                 lora_prefill: str = "library"):
         if prefill_gemm not in ("library", "mxfp4"):
             raise ValueError(f"unknown prefill_gemm {prefill_gemm!r} "
                              "(expected 'library' or 'mxfp4')")
+        if lora_prefill not in ("library", "sgmv"):
+            raise ValueError(f"unknown lora_prefill {lora_prefill!r} "
+                             "(expected 'library' or 'sgmv')")
         device_type = torch.device(
             device or ("cuda:0" if torch.cuda.is_available() else "cpu")).type
         if prefill_gemm == "mxfp4" and not (
@@ -639,6 +643,13 @@ class LlamaDecodeEngine:
             self.buf_lora_t = torch.zeros(B, lora.rank,
                                           dtype=torch.float32,
                                           device=self.device)
+        # "library": a prefill adds the adapters' deltas with f32 library
+        # GEMMs, one masked pass per distinct id; "sgmv": with the
+        # segmented ops.lora_sgmv_shrink / lora_sgmv_expand pair over a
+        # tile table built on the host, into a t buffer that grows to
+        # the largest prefill seen
+        self.lora_prefill = lora_prefill
+        self._sgmv_t = None
         # per-request sampling (opt-in): every slot carries its own
         # parameters in device buffers read by ops.sample_tokens, so one
         # captured graph serves rows that sample differently.  Defaults:
@@ -971,8 +982,10 @@ class LlamaDecodeEngine:
         (-1 = base), record them in buf_adapter for ``slots`` and return
         the plan _lora_prefill consumes — a list of (id, row mask or
         None), one entry per DISTINCT adapter id of the call, with
-        counts[i] token rows for prompt i.  None when no row is adapted.
-        The host knows the ids, so nothing here syncs."""
+        counts[i] token rows for prompt i; under ``lora_prefill="sgmv"``
+        the ops.lora_sgmv_tiles table of the call instead.  None when no
+        row is adapted.  The host knows the ids, so nothing here
+        syncs."""
         if adapters is None:
             if self.lora is not None:
                 self.buf_adapter[slots] = -1
@@ -985,6 +998,8 @@ class LlamaDecodeEngine:
         distinct = sorted({a for a in ids if a >= 0})
         if not distinct:
             return None
+        if self.lora_prefill == "sgmv":
+            return ops.lora_sgmv_tiles(counts, ids, self.device)
         if len(set(ids)) == 1:
             return [(distinct[0], None)]  # every row, no mask needed
         row_ids = torch.tensor(
@@ -1002,12 +1017,28 @@ class LlamaDecodeEngine:
         if plan is None:
             return y
         a_tab, b_tab = self.lora.layers[li][proj]
+        if self.lora_prefill == "sgmv":
+            return self._lora_prefill_sgmv(plan, a_tab, b_tab, x, y)
         xf = x.float()
         for a, mask in plan:
             delta = (xf @ a_tab[a].float().t()) @ b_tab[a].float().t()
             new = (y.float() + delta).to(y.dtype)
             y = new if mask is None else torch.where(mask, new, y)
         return y
+
+    def _lora_prefill_sgmv(self, tiles, a_tab, b_tab, x, y):
+        """The ``lora_prefill="sgmv"`` form of _lora_prefill: two
+        launches over the call's tile table, whatever the number of
+        adapters; base rows are in no tile and cost nothing.  t lives in
+        an engine-owned buffer reused by every projection and layer."""
+        T = x.shape[0]
+        if self._sgmv_t is None or self._sgmv_t.shape[0] < T:
+            self._sgmv_t = torch.zeros(T, self.lora.rank,
+                                       dtype=torch.float32,
+                                       device=self.device)
+        t = self._sgmv_t[:T]
+        ops.lora_sgmv_shrink(x.contiguous(), a_tab, tiles, out=t)
+        return ops.lora_sgmv_expand(y.contiguous(), t, b_tab, tiles)
 
     # ---------------------------------------------------------- decode
     def _decode_step_body(self):
@@ -1329,7 +1360,8 @@ class LlamaDecodeEngine:
         ``prefill_gemm="mxfp4"`` prefill and decode both run on the
         packs, so an mxfp4w engine then holds 4.25 bits per weight.
         Engines that share these weights and packs (replicas) keep
-        working.  Afterwards rebuild_weight_packs(), weights.state_dict()
+        working, and so do adapters under either ``lora_prefill``: the
+        LoRA tables are no masters and stay.  Afterwards rebuild_weight_packs(), weights.state_dict()
         and weights.load_state_dict() raise ValueError."""
         if self.prefill_gemm != "mxfp4":
             raise ValueError(
@@ -1967,6 +1999,12 @@ class LlamaServer:
       adapters.  ``max_adapters`` (default: their number) sizes the
       tables, ``lora_rank`` (8/16/32/64) is the table rank.  Not with
       ``speculative > 0``.  Adapters are fixed once ``load()`` ran.
+    - ``lora_prefill``: how a prefill adds the adapters' deltas —
+      "library" (default) with f32 library GEMMs, one masked pass per
+      distinct adapter of the call; "sgmv" with the segmented
+      ``ops.lora_sgmv_shrink`` / ``ops.lora_sgmv_expand`` HIP pair, two
+      launches per projection whatever the number of adapters.  Passed
+      to every engine; the decode step is the same under both.
     - ``sampling``: "engine" (default) picks tokens with the engine-wide
       ``temperature`` / ``top_k``; "request" gives every request its own
       ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``seed`` and
@@ -2013,7 +2051,8 @@ class LlamaServer:
                  logit_processors: bool = False,
                  prefix_cache_blocks: int = 0,
                  prefill_gemm: str = "library",
-                 release_masters: bool = False, **class_args):
+                 release_masters: bool = False,
+                 lora_prefill: str = "library", **class_args):
         import queue as queue_mod
         import threading
 
@@ -2061,6 +2100,10 @@ class LlamaServer:
                 f"max_adapters={self.max_adapters} is below the "
                 f"{len(self.adapters)} adapters configured")
         self.lora_rank = int(lora_rank)
+        if lora_prefill not in ("library", "sgmv"):
+            raise ValueError(f"unknown lora_prefill {lora_prefill!r} "
+                             "(expected 'library' or 'sgmv')")
+        self.lora_prefill = lora_prefill
         self._lora_requests = {name: 0 for name in self.adapters}
         self._lora_lock = threading.Lock()
         if sampling not in ("engine", "request"):
@@ -2215,7 +2258,8 @@ class LlamaServer:
                                   sampling=self.sampling,
                                   logit_processors=self.logit_processors,
                                   prefix_cache_blocks=self.prefix_cache_blocks,
-                                  prefill_gemm=self.prefill_gemm)
+                                  prefill_gemm=self.prefill_gemm,
+                                  lora_prefill=self.lora_prefill)
         self.engines = [first]
         for _ in range(self.replicas - 1):
             replica = LlamaDecodeEngine(
@@ -2225,7 +2269,8 @@ class LlamaServer:
                 temperature=engine_temp, top_k=engine_top_k,
                 lora=first.lora, sampling=self.sampling,
                 logit_processors=self.logit_processors,
-                prefix_cache_blocks=self.prefix_cache_blocks)
+                prefix_cache_blocks=self.prefix_cache_blocks,
+                lora_prefill=self.lora_prefill)
             replica.weight_dtype = first.weight_dtype
             replica.prefill_gemm = first.prefill_gemm
             replica._fp8_packs = first._fp8_packs  # shared packs

@@ -3,7 +3,7 @@
 # Licensed under the Apache License, Version 2.0 (the "License");
 # you may not use this file except in compliance with the License.
 """GPU ops: python dispatch over the in-tree HIP extension
-(mlrun_amd._hip_ops, built from ops/hip/kernels.hip for gfx950).
+(mlrun_amd._hip_ops, built from ops/hip/*.hip for gfx950).
 
 Dispatch policy:
 - tensors on GPU  -> the HIP extension MUST be present; a missing
@@ -1017,6 +1017,139 @@ def lora_expand(y: torch.Tensor, t: torch.Tensor, Bm: torch.Tensor,
     for b, a in enumerate(idx.tolist()):
         if 0 <= a < NA:
             y[b] = (y[b].float() + Bm[a].float() @ t[b]).to(y.dtype)
+    return y
+
+
+# multi-LoRA prefill: segmented (SGMV) pair over a host-built tile table
+
+LORA_SGMV_TILE = 16            # token rows per tile (one MFMA operand)
+
+
+def lora_sgmv_tiles(counts, ids, device=None) -> torch.Tensor:
+    """Tile table of a packed prefill for lora_sgmv_shrink / _expand:
+    prompt i has counts[i] consecutive token rows and adapter ids[i]
+    (-1 = base model).  Adjacent prompts of one id merge into a segment,
+    a segment is cut into 16-row tiles (its last tile may be shorter),
+    and base segments give no tiles.  Returns int32 [ntiles, 3] rows
+    (row0, nrows, adapter) on ``device``; built from host values only,
+    so nothing here syncs."""
+    counts = [int(c) for c in counts]
+    ids = [int(a) for a in ids]
+    if len(counts) != len(ids) or any(c < 0 for c in counts):
+        raise ValueError("lora_sgmv_tiles: one id per prompt and counts "
+                         ">= 0")
+    segments = []                       # [row0, nrows, id], merged
+    row = 0
+    for count, a in zip(counts, ids):
+        if count and segments and segments[-1][2] == a:
+            segments[-1][1] += count
+        elif count:
+            segments.append([row, count, a])
+        row += count
+    tiles = [(r, min(LORA_SGMV_TILE, row0 + n - r), a)
+             for row0, n, a in segments if a >= 0
+             for r in range(row0, row0 + n, LORA_SGMV_TILE)]
+    return torch.tensor(tiles, dtype=torch.int32).reshape(-1, 3).to(
+        device or "cpu")
+
+
+def _check_lora_sgmv(rows, t, table, tiles, width_name, width_mod):
+    """Shared argument checks of lora_sgmv_shrink / lora_sgmv_expand:
+    rows is the bf16 [T, width] activation (x or y), table the bf16
+    [NA, ., .] adapter table, t the f32 [T, R] intermediate."""
+    for name, tensor, dtype in (("rows", rows, torch.bfloat16),
+                                ("table", table, torch.bfloat16),
+                                ("t", t, torch.float32),
+                                ("tiles", tiles, torch.int32)):
+        if tensor.dtype != dtype:
+            raise ValueError(f"lora_sgmv: {name} must be {dtype}, got "
+                             f"{tensor.dtype}")
+        if not tensor.is_contiguous():
+            raise ValueError(f"lora_sgmv: {name} must be contiguous")
+        if tensor.device != rows.device:
+            raise ValueError(f"lora_sgmv: {name} is on {tensor.device}, "
+                             f"rows on {rows.device}")
+    if rows.dim() != 2 or t.dim() != 2 or table.dim() != 3:
+        raise ValueError("lora_sgmv: expected rows [T, width], t [T, R] "
+                         "and a 3-d table")
+    if tiles.dim() != 2 or tiles.shape[1] != 3:
+        raise ValueError("lora_sgmv: tiles must be [ntiles, 3], got "
+                         f"{tuple(tiles.shape)}")
+    if t.shape[0] != rows.shape[0]:
+        raise ValueError("lora_sgmv: rows and t must agree on T")
+    if t.shape[1] not in LORA_RANKS:
+        raise ValueError(f"lora_sgmv: R must be one of {LORA_RANKS}, got "
+                         f"{t.shape[1]}")
+    if rows.shape[1] == 0 or rows.shape[1] % width_mod:
+        raise ValueError(f"lora_sgmv: {width_name} must be a positive "
+                         f"multiple of {width_mod}, got {rows.shape[1]}")
+
+
+def _sgmv_live_tiles(tiles, T, NA):
+    """The tiles the kernels serve: adapter in [0, NA), 1 <= nrows <= 16,
+    rows inside [0, T); every other one is skipped."""
+    return [(r0, n, a) for r0, n, a in tiles.tolist()
+            if 0 <= a < NA and 1 <= n <= LORA_SGMV_TILE
+            and 0 <= r0 <= T - n]
+
+
+def lora_sgmv_shrink(x: torch.Tensor, A: torch.Tensor, tiles: torch.Tensor,
+                     out: torch.Tensor = None) -> torch.Tensor:
+    """Multi-LoRA shrink for prefill rows grouped by adapter: for every
+    tile (row0, nrows, a) of ``tiles`` (lora_sgmv_tiles),
+    t[r, j] = sum_k x[r, k] * A[a, j, k] over its rows, f32 accumulation.
+
+    x [T, K] bf16 (K % 32 == 0), A [NA, R, K] bf16 with R in {8, 16, 32,
+    64}, tiles [ntiles, 3] int32.  Returns t [T, R] f32 (``out`` when
+    given: nothing is allocated then).  Rows that no tile covers keep
+    their t row, and their x row and unnamed table slots are not read; a
+    tile with an adapter outside [0, NA), nrows outside [1, 16] or rows
+    outside [0, T) is skipped.  A row's sum order does not depend on the
+    rest of the call.  Bad shapes, dtypes or layouts raise ValueError."""
+    if A.dim() != 3:
+        raise ValueError("lora_sgmv_shrink: A must be [NA, R, K]")
+    if out is None:
+        out = torch.zeros(x.shape[0], A.shape[1], dtype=torch.float32,
+                          device=x.device)
+    _check_lora_sgmv(x, out, A, tiles, "K", 32)
+    if A.shape[1] != out.shape[1] or A.shape[2] != x.shape[1]:
+        raise ValueError("lora_sgmv_shrink: A must be [NA, R, K] matching "
+                         "x [T, K] and t [T, R]")
+    if tiles.shape[0] == 0:
+        return out
+    if x.is_cuda:
+        _require_hip().lora_sgmv_shrink(out, x, A, tiles)
+        return out
+    for r0, n, a in _sgmv_live_tiles(tiles, x.shape[0], A.shape[0]):
+        out[r0:r0 + n] = x[r0:r0 + n].float() @ A[a].float().t()
+    return out
+
+
+def lora_sgmv_expand(y: torch.Tensor, t: torch.Tensor, Bm: torch.Tensor,
+                     tiles: torch.Tensor) -> torch.Tensor:
+    """Multi-LoRA expand for prefill rows grouped by adapter, in place:
+    for every tile (row0, nrows, a), y[r, n] = bf16(float(y[r, n]) +
+    sum_j t[r, j] * Bm[a, n, j]) over its rows — f32 accumulation, one
+    rounding, the contract of lora_expand.
+
+    y [T, N] bf16 (N % 8 == 0), t [T, R] f32, Bm [NA, N, R] bf16
+    (alpha / r already folded in), tiles [ntiles, 3] int32.  Rows that no
+    tile covers are left untouched and their t row is not read; tiles
+    are skipped as in lora_sgmv_shrink.  Returns y."""
+    if Bm.dim() != 3:
+        raise ValueError("lora_sgmv_expand: Bm must be [NA, N, R]")
+    _check_lora_sgmv(y, t, Bm, tiles, "N", 8)
+    if Bm.shape[1] != y.shape[1] or Bm.shape[2] != t.shape[1]:
+        raise ValueError("lora_sgmv_expand: Bm must be [NA, N, R] matching "
+                         "y [T, N] and t [T, R]")
+    if tiles.shape[0] == 0:
+        return y
+    if y.is_cuda:
+        _require_hip().lora_sgmv_expand(y, t, Bm, tiles)
+        return y
+    for r0, n, a in _sgmv_live_tiles(tiles, y.shape[0], Bm.shape[0]):
+        y[r0:r0 + n] = (y[r0:r0 + n].float() +
+                        t[r0:r0 + n] @ Bm[a].float().t()).to(y.dtype)
     return y
 
 

@@ -734,6 +734,62 @@ void lora_expand(torch::Tensor y, torch::Tensor t, torch::Tensor Bm,
                      (int)t.size(1), (int)y.size(1), stream());
 }
 
+// multi-LoRA prefill (SGMV): shared shape checks of the two kernels
+static void check_lora_sgmv(const torch::Tensor& act, const torch::Tensor& t,
+                            const torch::Tensor& table,
+                            const torch::Tensor& tiles, int64_t width_mod,
+                            const char* width_name) {
+  TORCH_CHECK(act.dim() == 2 && t.dim() == 2 && table.dim() == 3,
+              "lora_sgmv: expected 2-d rows, t [T, R] and a [NA, ., .] "
+              "table");
+  TORCH_CHECK(tiles.dim() == 2 && tiles.size(1) == 3,
+              "lora_sgmv: tiles must be [ntiles, 3]");
+  int64_t T = act.size(0), R = t.size(1), width = act.size(1);
+  TORCH_CHECK(t.size(0) == T, "lora_sgmv: rows and t must agree on T");
+  TORCH_CHECK(R == 8 || R == 16 || R == 32 || R == 64,
+              "lora_sgmv: rank must be 8, 16, 32 or 64, got ", R);
+  TORCH_CHECK(width > 0 && width % width_mod == 0, "lora_sgmv: ",
+              width_name, " must be a positive multiple of ", width_mod,
+              ", got ", width);
+  TORCH_CHECK(T < (1LL << 24) && table.size(0) < (1LL << 20) &&
+              width < (1LL << 24) && tiles.size(0) < (1LL << 24),
+              "lora_sgmv: shape too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(act.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0,
+              "lora_sgmv: rows, t and tables must be 16-byte aligned");
+}
+
+void lora_sgmv_shrink(torch::Tensor t, torch::Tensor x, torch::Tensor A,
+                      torch::Tensor tiles) {
+  CHECK_DEV(t); CHECK_CONTIG(t); CHECK_F32(t);
+  CHECK_DEV(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_DEV(A); CHECK_CONTIG(A); CHECK_BF16(A);
+  CHECK_DEV(tiles); CHECK_CONTIG(tiles); CHECK_I32(tiles);
+  check_lora_sgmv(x, t, A, tiles, 32, "K");
+  TORCH_CHECK(A.size(1) == t.size(1) && A.size(2) == x.size(1),
+              "lora_sgmv_shrink: A must be [NA, R, K]");
+  launch_lora_sgmv_shrink(t.data_ptr(), x.data_ptr(), A.data_ptr(),
+                          tiles.data_ptr(), (int)tiles.size(0),
+                          (int)x.size(0), (int)A.size(0), (int)t.size(1),
+                          (int)x.size(1), stream());
+}
+
+void lora_sgmv_expand(torch::Tensor y, torch::Tensor t, torch::Tensor Bm,
+                      torch::Tensor tiles) {
+  CHECK_DEV(y); CHECK_CONTIG(y); CHECK_BF16(y);
+  CHECK_DEV(t); CHECK_CONTIG(t); CHECK_F32(t);
+  CHECK_DEV(Bm); CHECK_CONTIG(Bm); CHECK_BF16(Bm);
+  CHECK_DEV(tiles); CHECK_CONTIG(tiles); CHECK_I32(tiles);
+  check_lora_sgmv(y, t, Bm, tiles, 8, "N");
+  TORCH_CHECK(Bm.size(1) == y.size(1) && Bm.size(2) == t.size(1),
+              "lora_sgmv_expand: Bm must be [NA, N, R]");
+  launch_lora_sgmv_expand(y.data_ptr(), t.data_ptr(), Bm.data_ptr(),
+                          tiles.data_ptr(), (int)tiles.size(0),
+                          (int)y.size(0), (int)Bm.size(0), (int)t.size(1),
+                          (int)y.size(1), stream());
+}
+
 // fused per-request sampler: one workgroup per logits row
 void sample_tokens(torch::Tensor logits, torch::Tensor pos,
                    torch::Tensor temperature, torch::Tensor top_k,
@@ -1021,6 +1077,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_expand", &lora_expand, py::arg("y"), py::arg("t"),
         py::arg("bm"), py::arg("idx"),
         "multi-LoRA expand: y[b] += Bm[idx[b]] @ t[b], in place (bf16)");
+  m.def("lora_sgmv_shrink", &lora_sgmv_shrink, py::arg("t"), py::arg("x"),
+        py::arg("a"), py::arg("tiles"),
+        "multi-LoRA prefill shrink: t[rows] = x[rows] @ A[a]^T per tile");
+  m.def("lora_sgmv_expand", &lora_sgmv_expand, py::arg("y"), py::arg("t"),
+        py::arg("bm"), py::arg("tiles"),
+        "multi-LoRA prefill expand: y[rows] += t[rows] @ Bm[a]^T per tile, "
+        "in place (bf16)");
   m.def("sample_tokens", &sample_tokens, py::arg("logits"), py::arg("pos"),
         py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
         py::arg("min_p"), py::arg("seed"), py::arg("out_tokens"),

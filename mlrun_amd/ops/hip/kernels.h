@@ -137,6 +137,16 @@ void launch_lora_expand(void* y, const void* t, const void* Bm,
                         const void* idx, int B, int NA, int R, int N,
                         void* stream);
 
+// multi-LoRA prefill (SGMV, lora_sgmv.hip): tiles int32 [ntiles, 3] =
+// (row0, nrows <= 16, adapter)
+void launch_lora_sgmv_shrink(void* t, const void* x, const void* A,
+                             const void* tiles, int ntiles, int T, int NA,
+                             int R, int K, void* stream);
+
+void launch_lora_sgmv_expand(void* y, const void* t, const void* Bm,
+                             const void* tiles, int ntiles, int T, int NA,
+                             int R, int N, void* stream);
+
 void launch_sample_tokens(const void* logits, const void* pos,
                           const void* temperature, const void* top_k,
                           const void* top_p, const void* min_p,

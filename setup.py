@@ -30,6 +30,7 @@ setup(
             sources=[
                 "mlrun_amd/ops/hip/bindings.cpp",
                 "mlrun_amd/ops/hip/kernels.hip",
+                "mlrun_amd/ops/hip/lora_sgmv.hip",
             ],
             extra_compile_args={
                 "cxx": ["-O3"],
