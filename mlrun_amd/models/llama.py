@@ -373,12 +373,12 @@ class LoraTables:
         self.loaded.add(slot)
 
 
-MX4_PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
+PACKED_PROJECTIONS = ("wqkv", "wo", "wgu", "wdown")
 
 
-class _Mx4Packs(dict):
-    """The mxfp4 packs of an engine: (w4, w_scale) keyed by (layer index,
-    projection name) and by "lm_head", so that they outlive the masters
+class _WeightPacks(dict):
+    """The mxfp4 or fp8 packs of an engine: (codes, scales) keyed by (layer
+    index, projection name) and by "lm_head", so that they outlive the masters
     (the id of a freed tensor can be reused).  The engine itself looks
     packs up by these names only (``dict.get`` does not reach
     ``__missing__``).  ``packs[id(master)]``, the key from before the
@@ -397,7 +397,7 @@ class _Mx4Packs(dict):
             if id(w.lm_head) == key:
                 return self["lm_head"]
             for li, layer in enumerate(w.layers):
-                for name in MX4_PROJECTIONS:
+                for name in PACKED_PROJECTIONS:
                     if id(layer[name]) == key:
                         return self[(li, name)]
         raise KeyError(key)
@@ -448,9 +448,9 @@ class LlamaDecodeEngine:
                  prefix_cache_blocks: int = 0,
                  prefill_gemm: str = "library",
                  lora_prefill: str = "library"):
-        if prefill_gemm not in ("library", "mxfp4"):
+        if prefill_gemm not in ("library", "mxfp4", "fp8"):
             raise ValueError(f"unknown prefill_gemm {prefill_gemm!r} "
-                             "(expected 'library' or 'mxfp4')")
+                             "(expected 'library', 'mxfp4' or 'fp8')")
         if lora_prefill not in ("library", "sgmv"):
             raise ValueError(f"unknown lora_prefill {lora_prefill!r} "
                              "(expected 'library' or 'sgmv')")
@@ -464,6 +464,13 @@ class LlamaDecodeEngine:
                 f"GPU, got weight_dtype={weight_dtype!r} on {device_type} "
                 f"with tp_size={tp_size}: there are no mxfp4 packs to run "
                 "on")
+        if prefill_gemm == "fp8" and not (
+                weight_dtype == "fp8w" and device_type == "cuda"
+                and tp_size == 1):
+            raise ValueError(
+                f'prefill_gemm="fp8" needs weight_dtype="fp8w" on one GPU, '
+                f"got weight_dtype={weight_dtype!r} on {device_type} with "
+                f"tp_size={tp_size}: there are no fp8 packs to run on")
         if sampling not in ("engine", "request"):
             raise ValueError(f"unknown sampling mode {sampling!r} "
                              "(expected 'engine' or 'request')")
@@ -588,11 +595,12 @@ class LlamaDecodeEngine:
                                    device=self.device)
         self.scale = 1.0 / math.sqrt(d)
         self._capture_stream_ctx = None
-        # opt-in fp8-weight decode: per-row e4m3 packs keyed by the
-        # bf16 master tensor (prefill stays bf16/hipBLASLt; ~7.5 GB
-        # extra for the packs on 8B — 288 GB HBM absorbs it)
+        # opt-in fp8-weight decode: per-row e4m3 packs keyed by (layer,
+        # projection) / "lm_head" (~7.5 GB for the packs on 8B; under
+        # prefill_gemm="library" the prefills still read the bf16
+        # masters, which then stay resident beside them)
         self.weight_dtype = weight_dtype
-        self._fp8_packs = {}
+        self._fp8_packs = _WeightPacks()
         if weight_dtype == "fp8w" and self.on_gpu and tp_size == 1:
             max_k = max(h, w.inter, w.hq * d)
             self.buf_a8 = torch.empty(B * max_k, dtype=torch.uint8,
@@ -608,13 +616,13 @@ class LlamaDecodeEngine:
             self.rebuild_fp8_packs()
         # opt-in mxfp4-weight decode (W4A16): OCP MXFP4 packs keyed the
         # same way; activations stay bf16, so no sidecars exist here
-        self._mx4_packs = _Mx4Packs()
+        self._mx4_packs = _WeightPacks()
         if weight_dtype == "mxfp4w":
             self.rebuild_weight_packs()
         # "library": the prefills multiply by the bf16 masters (hipBLASLt);
-        # "mxfp4": they run ops.gemm_mxfp4 on the packs the decode step
-        # reads, so one model serves both phases and the masters can go
-        # (release_master_weights)
+        # "mxfp4" / "fp8": they run ops.gemm_mxfp4 / ops.gemm_fp8 on the
+        # packs the decode step reads, so one model serves both phases
+        # and the masters can go (release_master_weights)
         self.prefill_gemm = prefill_gemm
         # fill-based (ns4 at B=32): the graph bakes ONE nsplit for all
         # context lengths, and decode mostly runs at S << max_seq_len —
@@ -868,6 +876,8 @@ class LlamaDecodeEngine:
 
     # ------------------------------------------------------------ gemm
     def _plan(self, w_):
+        """(ksplit, variant) of the decode GEMM with a weight of w_'s
+        [N, K] (a master, or the codes of an fp8 pack)."""
         key = (w_.shape[0], w_.shape[1])
         if key not in self._ksplits:
             self._ksplits[key] = ops.pick_gemm_plan(self.B, *key)
@@ -890,18 +900,18 @@ class LlamaDecodeEngine:
                                            a.shape[1])
             return ops.skinny_gemm_mxfp4(a, pack[0], pack[1], out=out,
                                          c_f32=self.buf_c32, ksplit=ksplit)
-        w_ = self._master(key)
-        pack = self._fp8_packs.get(id(w_))
+        pack = self._fp8_packs.get(key)
         if pack is not None:
             M, K = a.shape
             if a8 is None:
                 a8 = self.buf_a8.narrow(0, 0, M * K).view(M, K)
                 ops.quant_fp8_rows(a, a8, self.buf_a_scale)
                 a_scale = self.buf_a_scale
-            ksplit, _ = self._plan(w_)
+            ksplit, _ = self._plan(pack[0])     # the codes are [N, K] too
             return ops.skinny_gemm_fp8(a8, a_scale, pack[0],
                                        pack[1], out=out,
                                        c_f32=self.buf_c32, ksplit=ksplit)
+        w_ = self._master(key)
         ksplit, variant = self._plan(w_)
         return ops.skinny_gemm(a, w_, out=out, c_f32=self.buf_c32,
                                ksplit=ksplit, variant=variant)
@@ -1078,9 +1088,10 @@ class LlamaDecodeEngine:
         on = self.on_gpu and self.tp_size == 1 and mode != "none"
         use_slabs = on and self.weight_dtype == "bf16" and \
             self.kv_dtype == "bf16"  # qkv slab (bf16 caches only)
-        # (the slab GEMM reads the bf16 masters: never under mxfp4w)
+        # (the slab GEMM reads the bf16 masters: never under mxfp4w, nor
+        # once an fp8w engine has released them)
         use_norm_slabs = on and mode == "all" and \
-            self.weight_dtype != "mxfp4w"
+            self.weight_dtype != "mxfp4w" and not w.masters_released
         # bit-exact decode fusions (bf16 weights, GPU, TP=1, no LoRA):
         # MLRUN_DECODE_FUSE is a comma list of
         #   norm    wo / down: split-K slabs folded inside the residual-
@@ -1329,13 +1340,13 @@ class LlamaDecodeEngine:
                                                self.tp_size == 1):
             return
         w = self.weights
-        self._fp8_packs = {}
-        for layer in w.layers:
-            for key in ("wqkv", "wo", "wgu", "wdown"):
-                self._fp8_packs[id(layer[key])] = \
-                    ops.quantize_fp8_weight(layer[key])
-        self._fp8_packs[id(w.lm_head)] = \
-            ops.quantize_fp8_weight(w.lm_head)
+        w._check_masters("rebuild_fp8_packs")
+        self._fp8_packs = _WeightPacks(w)
+        for li, layer in enumerate(w.layers):
+            for name in PACKED_PROJECTIONS:
+                self._fp8_packs[(li, name)] = \
+                    ops.quantize_fp8_weight(layer[name])
+        self._fp8_packs["lm_head"] = ops.quantize_fp8_weight(w.lm_head)
 
     def rebuild_weight_packs(self):
         """(Re)quantize the packs of the engine's weight mode (fp8w or
@@ -1347,9 +1358,9 @@ class LlamaDecodeEngine:
             return
         w = self.weights
         w._check_masters("rebuild_weight_packs")
-        self._mx4_packs = _Mx4Packs(w)
+        self._mx4_packs = _WeightPacks(w)
         for li, layer in enumerate(w.layers):
-            for name in MX4_PROJECTIONS:
+            for name in PACKED_PROJECTIONS:
                 self._mx4_packs[(li, name)] = \
                     ops.quantize_mxfp4_weight(layer[name])
         self._mx4_packs["lm_head"] = ops.quantize_mxfp4_weight(w.lm_head)
@@ -1357,23 +1368,25 @@ class LlamaDecodeEngine:
     def release_master_weights(self):
         """Free the bf16 wqkv / wo / wgu / wdown of every layer and
         lm_head (embedding and norm weights stay): with
-        ``prefill_gemm="mxfp4"`` prefill and decode both run on the
-        packs, so an mxfp4w engine then holds 4.25 bits per weight.
+        ``prefill_gemm="mxfp4"`` / ``"fp8"`` prefill and decode both run
+        on the packs, so an mxfp4w engine then holds 4.25 bits per weight
+        and an fp8w engine 8 bits plus one f32 scale per row.
         Engines that share these weights and packs (replicas) keep
         working, and so do adapters under either ``lora_prefill``: the
-        LoRA tables are no masters and stay.  Afterwards rebuild_weight_packs(), weights.state_dict()
+        LoRA tables are no masters and stay.  Afterwards
+        rebuild_weight_packs() / rebuild_fp8_packs(), weights.state_dict()
         and weights.load_state_dict() raise ValueError."""
-        if self.prefill_gemm != "mxfp4":
+        if self.prefill_gemm not in ("mxfp4", "fp8"):
             raise ValueError(
-                "release_master_weights() needs prefill_gemm=\"mxfp4\", "
-                f"got prefill_gemm={self.prefill_gemm!r}: the library "
-                "prefill reads the bf16 masters")
+                "release_master_weights() needs prefill_gemm=\"mxfp4\" or "
+                f"\"fp8\", got prefill_gemm={self.prefill_gemm!r}: the "
+                "library prefill reads the bf16 masters")
         w = self.weights
         if w.masters_released:
             return
         w.masters_released = True
         for layer in w.layers:
-            for name in MX4_PROJECTIONS:
+            for name in PACKED_PROJECTIONS:
                 layer[name] = None
         w.lm_head = None
 
@@ -1426,9 +1439,15 @@ class LlamaDecodeEngine:
 
     def _prefill_project(self, plan):
         """_run_layers' ``project`` of the prefills: the library GEMM
-        on the masters, or ops.gemm_mxfp4 on the packs under
-        ``prefill_gemm="mxfp4"``, plus the LoRA deltas of ``plan``."""
+        on the masters, or ops.gemm_mxfp4 / ops.gemm_fp8 on the packs
+        under ``prefill_gemm="mxfp4"`` / ``"fp8"``, plus the LoRA deltas
+        of ``plan``."""
         layers = self.weights.layers
+        if self.prefill_gemm == "fp8":
+            def project(li, name, x):
+                return self._lora_prefill(plan, li, name, x, self._fp8_rows(
+                    x, self._fp8_packs[(li, name)]))
+            return project
         if self.prefill_gemm == "mxfp4":
             def project(li, name, x):
                 return self._lora_prefill(plan, li, name, x, ops.gemm_mxfp4(
@@ -1440,8 +1459,16 @@ class LlamaDecodeEngine:
                                       x @ layers[li][name].t())
         return project
 
+    def _fp8_rows(self, x, pack):
+        """x [T, K] bf16 times an fp8 pack, as the decode step computes
+        it: per-row dynamic e4m3 codes, then the W8A8 GEMM."""
+        a8, a_scale = ops.quant_fp8_rows(x.contiguous())
+        return ops.gemm_fp8(a8, a_scale, *pack)
+
     def _prefill_logits(self, last):
         """Logits of the prefills' last-token rows ``last`` [n, H]."""
+        if self.prefill_gemm == "fp8":
+            return self._fp8_rows(last, self._fp8_packs["lm_head"])
         if self.prefill_gemm == "mxfp4":
             return ops.gemm_mxfp4(last.contiguous(),
                                   *self._mx4_packs["lm_head"])
@@ -2032,10 +2059,13 @@ class LlamaServer:
     - ``prefill_gemm``: "library" (default) prefills on the bf16 master
       weights; "mxfp4" (needs ``weight_dtype="mxfp4w"``) prefills with
       ``ops.gemm_mxfp4`` on the packs the decode step reads, so prompt
-      and generated tokens come from one model.  ``release_masters=True``
-      (needs ``prefill_gemm="mxfp4"``) then frees the bf16 projection
-      weights and lm_head once the checkpoint is loaded and packed:
-      the deployment holds 4.25 bits per weight.
+      and generated tokens come from one model; "fp8" (needs
+      ``weight_dtype="fp8w"``) does the same for the fp8 packs with
+      ``ops.quant_fp8_rows`` + ``ops.gemm_fp8``.  ``release_masters=True``
+      (needs ``prefill_gemm="mxfp4"`` or ``"fp8"``) then frees the bf16
+      projection weights and lm_head once the checkpoint is loaded and
+      packed: the deployment holds 4.25 (mxfp4w) or 8 (fp8w) bits per
+      weight.
     """
 
     def __init__(self, context=None, name=None, model_path=None,
@@ -2235,11 +2265,12 @@ class LlamaServer:
                 'prefill="packed" needs a bf16 KV cache (the packed '
                 'attention kernel does not read fp8 caches): use '
                 'kv_dtype="bf16" or prefill="exact"')
-        if self.release_masters and self.prefill_gemm != "mxfp4":
+        if self.release_masters and \
+                self.prefill_gemm not in ("mxfp4", "fp8"):
             raise ValueError(
-                "release_masters=True needs prefill_gemm=\"mxfp4\", got "
-                f"prefill_gemm={self.prefill_gemm!r}: the library prefill "
-                "reads the bf16 masters")
+                "release_masters=True needs prefill_gemm=\"mxfp4\" or "
+                f"\"fp8\", got prefill_gemm={self.prefill_gemm!r}: the "
+                "library prefill reads the bf16 masters")
         if not torch.cuda.is_available():
             self.replicas = 1
         # sampling="request": the engine-wide temperature / top_k stay

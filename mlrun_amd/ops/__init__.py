@@ -341,6 +341,10 @@ def skinny_gemm_fp8(a8: torch.Tensor, a_scale: torch.Tensor,
             c_f32 = _EMPTY_F32
         ops.skinny_gemm_fp8(out, c_f32, a8, a_scale, w8, w_scale, ksplit)
         return out
+    return _fp8_gemm_cpu(a8, a_scale, w8, w_scale, out)
+
+
+def _fp8_gemm_cpu(a8, a_scale, w8, w_scale, out):
     a = _fp8_pair_unswizzle(a8).view(torch.float8_e4m3fn).float() * \
         a_scale[:, None].float()
     w = _fp8_pair_unswizzle(w8).view(torch.float8_e4m3fn).float() * \
@@ -350,6 +354,67 @@ def skinny_gemm_fp8(a8: torch.Tensor, a_scale: torch.Tensor,
         out.copy_(result)
         return out
     return result
+
+
+def _check_fp8_gemm_args(a8, a_scale, w8, w_scale, out):
+    """The argument checks of gemm_fp8 (dtype, rank, contiguity, device,
+    the K rule, scale lengths, out, and on GPU the 16-byte alignment);
+    ValueError before any launch.  Returns M, N, K."""
+    for name, t, dtype, rank in (("a8", a8, torch.uint8, 2),
+                                 ("w8", w8, torch.uint8, 2),
+                                 ("a_scale", a_scale, torch.float32, 1),
+                                 ("w_scale", w_scale, torch.float32, 1)):
+        if t.dim() != rank or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {rank}-d {dtype} "
+                             f"tensor, got {tuple(t.shape)} {t.dtype}")
+        if t.device != a8.device:
+            raise ValueError(f"{name} is on {t.device}, a8 on {a8.device}")
+    M, K = a8.shape
+    N = w8.shape[0]
+    if M < 1 or N < 1:
+        raise ValueError(f"fp8 GEMM needs M, N >= 1, got M={M}, N={N}")
+    if K < 64 or K % 64:
+        raise ValueError(f"fp8 GEMM needs K % 64 == 0 and K >= 64, got K={K}")
+    if w8.shape[1] != K:
+        raise ValueError(f"a8 is [{M}, {K}]: w8 must be [N, {K}], got "
+                         f"{tuple(w8.shape)}")
+    if a_scale.numel() != M or w_scale.numel() != N:
+        raise ValueError(
+            f"a_scale must hold M={M} and w_scale N={N} scales, got "
+            f"{a_scale.numel()} / {w_scale.numel()}")
+    if out is not None and (
+            out.dtype != torch.bfloat16 or out.device != a8.device or
+            not out.is_contiguous() or tuple(out.shape) != (M, N)):
+        raise ValueError(f"out must be a contiguous bf16 [{M}, {N}] tensor "
+                         f"on {a8.device}")
+    if a8.is_cuda and (a8.data_ptr() % 16 or w8.data_ptr() % 16 or
+                       (out is not None and out.data_ptr() % 16)):
+        raise ValueError("a8, w8 and out must be 16-byte aligned")
+    return M, N, K
+
+
+def gemm_fp8(a8: torch.Tensor, a_scale: torch.Tensor, w8: torch.Tensor,
+             w_scale: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """out[M,N] bf16 = ((a8 . w8^T)[m, n] * a_scale[m]) * w_scale[n] for
+    ANY M >= 1: the W8A8 entry point of the fp8 prefill.  a8 / a_scale
+    are the codes of quant_fp8_rows, w8 / w_scale a pack of
+    quantize_fp8_weight.  On GPU M <= 64 runs skinny_gemm_fp8 at the
+    ksplit of pick_gemm_plan; larger M runs the output-tile kernel
+    gemm_fp8_tile_kernel (128 x 128 or 128 x 64 tiles, the launcher's
+    choice; LDS-DMA operands, the 128-k fp8 MFMA).  No split-K there:
+    one summation order whatever the grid.  With out given nothing is
+    allocated at M > 64; no sync."""
+    M, N, K = _check_fp8_gemm_args(a8, a_scale, w8, w_scale, out)
+    if not a8.is_cuda:
+        return _fp8_gemm_cpu(a8, a_scale, w8, w_scale, out)
+    if M <= 64:
+        return skinny_gemm_fp8(a8, a_scale, w8, w_scale, out=out,
+                               ksplit=pick_gemm_plan(M, N, K)[0])
+    ops = _require_hip()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a8.device)
+    ops.gemm_fp8_tile(out, a8, a_scale, w8, w_scale, 0)
+    return out
 
 
 # OCP MXFP4: e2m1 magnitudes by 3-bit code (the sign sits in bit 3), one

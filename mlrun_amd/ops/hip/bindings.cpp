@@ -402,6 +402,40 @@ void gemm_mxfp4_tile(torch::Tensor out_bf16, torch::Tensor a,
                          stream());
 }
 
+// any-M fp8 GEMM on output tiles (prefill); bn 0 = the launcher's choice
+void gemm_fp8_tile(torch::Tensor out_bf16, torch::Tensor a8,
+                   torch::Tensor a_scale, torch::Tensor w8,
+                   torch::Tensor w_scale, int64_t bn) {
+  CHECK_DEV(out_bf16); CHECK_CONTIG(out_bf16); CHECK_BF16(out_bf16);
+  CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
+  CHECK_DEV(w8); CHECK_CONTIG(w8); CHECK_U8(w8);
+  CHECK_DEV(a_scale); CHECK_CONTIG(a_scale); CHECK_F32(a_scale);
+  CHECK_DEV(w_scale); CHECK_CONTIG(w_scale); CHECK_F32(w_scale);
+  TORCH_CHECK(a8.dim() == 2 && w8.dim() == 2, "a8 and w8 must be 2-d");
+  TORCH_CHECK(a8.device() == out_bf16.device() &&
+              a8.device() == w8.device() &&
+              a8.device() == a_scale.device() &&
+              a8.device() == w_scale.device(),
+              "tensors on different devices");
+  int64_t M = a8.size(0), K = a8.size(1), N = w8.size(0);
+  // grid.y = ceil(M / 128) must stay below 65536
+  TORCH_CHECK(M >= 1 && M <= 128 * 65535 && N >= 1 && N <= INT_MAX - 128 &&
+              K >= 64 && K % 64 == 0 && K <= INT_MAX - 128,
+              "fp8 tile path needs M, N >= 1 and K % 64 == 0");
+  TORCH_CHECK(w8.size(1) == K, "a8 and w8 must agree on K");
+  TORCH_CHECK(a_scale.numel() == M && w_scale.numel() == N,
+              "a_scale must have M and w_scale N elements");
+  TORCH_CHECK(out_bf16.numel() == M * N, "out must hold M * N elements");
+  TORCH_CHECK(bn == 0 || bn == 64 || bn == 128, "bn must be 0, 64 or 128");
+  TORCH_CHECK((uintptr_t)a8.data_ptr() % 16 == 0 &&
+              (uintptr_t)w8.data_ptr() % 16 == 0 &&
+              (uintptr_t)out_bf16.data_ptr() % 16 == 0,
+              "a8, w8 and out must be 16-byte aligned");
+  launch_gemm_fp8_tile(out_bf16.data_ptr(), a8.data_ptr(),
+                       a_scale.data_ptr(), w8.data_ptr(), w_scale.data_ptr(),
+                       (int)M, (int)N, (int)K, (int)bn, stream());
+}
+
 void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
                     torch::Tensor a) {
   CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
@@ -1040,6 +1074,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "mxfp4-weight decode GEMM (e2m1 codes, E8M0 block scales, bf16 A)");
   m.def("gemm_mxfp4_tile", &gemm_mxfp4_tile,
         "mxfp4-weight GEMM for any M on 128-row output tiles (prefill)");
+  m.def("gemm_fp8_tile", &gemm_fp8_tile,
+        "fp8 W8A8 GEMM for any M on 128-row output tiles (prefill)");
   m.def("quant_fp8_rows", &quant_fp8_rows,
         "dynamic per-row bf16 -> fp8 e4m3 quantization");
   m.def("attn_decode", &attn_decode, py::arg("o"), py::arg("q"),

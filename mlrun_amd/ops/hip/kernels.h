@@ -80,6 +80,14 @@ void launch_gemm_mxfp4_tile(void* out_bf16, const void* A, const void* W4,
                             const void* w_scale, int M, int N, int K, int bn,
                             void* stream);
 
+// fp8 prefill GEMM (gemm_fp8_tile.hip): out[M,N] bf16 = (A8 . W8^T) *
+// a_scale[m] * w_scale[n] on the codes of quant_fp8_rows and the packs of
+// the decode kernel; any M, N >= 1, K % 64 == 0; bn = 0 lets the launcher
+// choose between 128 and 64
+void launch_gemm_fp8_tile(void* out_bf16, const void* A8, const void* a_scale,
+                          const void* W8, const void* w_scale, int M, int N,
+                          int K, int bn, void* stream);
+
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
                            int cols, void* stream);
 

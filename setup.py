@@ -31,6 +31,7 @@ setup(
                 "mlrun_amd/ops/hip/bindings.cpp",
                 "mlrun_amd/ops/hip/kernels.hip",
                 "mlrun_amd/ops/hip/lora_sgmv.hip",
+                "mlrun_amd/ops/hip/gemm_fp8_tile.hip",
             ],
             extra_compile_args={
                 "cxx": ["-O3"],
