@@ -448,9 +448,10 @@ class LlamaDecodeEngine:
                  prefix_cache_blocks: int = 0,
                  prefill_gemm: str = "library",
                  lora_prefill: str = "library"):
-        if prefill_gemm not in ("library", "mxfp4", "fp8"):
+        if prefill_gemm not in ("library", "mxfp4", "fp8", "bf16"):
             raise ValueError(f"unknown prefill_gemm {prefill_gemm!r} "
-                             "(expected 'library', 'mxfp4' or 'fp8')")
+                             "(expected 'library', 'mxfp4', 'fp8' or "
+                             "'bf16')")
         if lora_prefill not in ("library", "sgmv"):
             raise ValueError(f"unknown lora_prefill {lora_prefill!r} "
                              "(expected 'library' or 'sgmv')")
@@ -471,6 +472,13 @@ class LlamaDecodeEngine:
                 f'prefill_gemm="fp8" needs weight_dtype="fp8w" on one GPU, '
                 f"got weight_dtype={weight_dtype!r} on {device_type} with "
                 f"tp_size={tp_size}: there are no fp8 packs to run on")
+        if prefill_gemm == "bf16" and not (
+                weight_dtype == "bf16" and tp_size == 1):
+            raise ValueError(
+                f'prefill_gemm="bf16" needs weight_dtype="bf16" on one '
+                f"device, got weight_dtype={weight_dtype!r} with "
+                f"tp_size={tp_size}: ops.gemm_bf16 runs on the bf16 "
+                "weights the decode step reads")
         if sampling not in ("engine", "request"):
             raise ValueError(f"unknown sampling mode {sampling!r} "
                              "(expected 'engine' or 'request')")
@@ -1439,9 +1447,10 @@ class LlamaDecodeEngine:
 
     def _prefill_project(self, plan):
         """_run_layers' ``project`` of the prefills: the library GEMM
-        on the masters, or ops.gemm_mxfp4 / ops.gemm_fp8 on the packs
-        under ``prefill_gemm="mxfp4"`` / ``"fp8"``, plus the LoRA deltas
-        of ``plan``."""
+        on the masters (or ops.gemm_bf16 on them under
+        ``prefill_gemm="bf16"``), or ops.gemm_mxfp4 / ops.gemm_fp8 on the
+        packs under ``prefill_gemm="mxfp4"`` / ``"fp8"``, plus the LoRA
+        deltas of ``plan``."""
         layers = self.weights.layers
         if self.prefill_gemm == "fp8":
             def project(li, name, x):
@@ -1452,6 +1461,11 @@ class LlamaDecodeEngine:
             def project(li, name, x):
                 return self._lora_prefill(plan, li, name, x, ops.gemm_mxfp4(
                     x.contiguous(), *self._mx4_packs[(li, name)]))
+            return project
+        if self.prefill_gemm == "bf16":
+            def project(li, name, x):
+                return self._lora_prefill(plan, li, name, x, ops.gemm_bf16(
+                    x.contiguous(), layers[li][name]))
             return project
 
         def project(li, name, x):
@@ -1472,6 +1486,8 @@ class LlamaDecodeEngine:
         if self.prefill_gemm == "mxfp4":
             return ops.gemm_mxfp4(last.contiguous(),
                                   *self._mx4_packs["lm_head"])
+        if self.prefill_gemm == "bf16":
+            return ops.gemm_bf16(last.contiguous(), self.weights.lm_head)
         return last @ self.weights.lm_head.t()
 
     def _dense_attend(self, rows, B, S):
@@ -2061,7 +2077,12 @@ class LlamaServer:
       ``ops.gemm_mxfp4`` on the packs the decode step reads, so prompt
       and generated tokens come from one model; "fp8" (needs
       ``weight_dtype="fp8w"``) does the same for the fp8 packs with
-      ``ops.quant_fp8_rows`` + ``ops.gemm_fp8``.  ``release_masters=True``
+      ``ops.quant_fp8_rows`` + ``ops.gemm_fp8``; "bf16" (needs
+      ``weight_dtype="bf16"``) keeps the bf16 weights and runs the
+      prefill GEMMs on ``ops.gemm_bf16`` instead of the library: its
+      tile kernel sums every output in one fixed order whatever the
+      request is packed with (slower than the library; see
+      docs/kernels.md).  ``release_masters=True``
       (needs ``prefill_gemm="mxfp4"`` or ``"fp8"``) then frees the bf16
       projection weights and lm_head once the checkpoint is loaded and
       packed: the deployment holds 4.25 (mxfp4w) or 8 (fp8w) bits per

@@ -265,6 +265,65 @@ def skinny_gemm(a: torch.Tensor, w: torch.Tensor,
     return result
 
 
+def _check_bf16_gemm_args(a, w, out):
+    """The argument checks of gemm_bf16 (dtype, rank, contiguity, device,
+    the K rule, out, and on GPU the 16-byte alignment); ValueError before
+    any launch.  Returns M, N, K."""
+    for name, t in (("a", a), ("w", w)):
+        if t.dim() != 2 or t.dtype != torch.bfloat16 or \
+                not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 2-d bf16 tensor, "
+                             f"got {tuple(t.shape)} {t.dtype}")
+    if w.device != a.device:
+        raise ValueError(f"w is on {w.device}, a on {a.device}")
+    M, K = a.shape
+    N = w.shape[0]
+    if M < 1 or N < 1:
+        raise ValueError(f"bf16 GEMM needs M, N >= 1, got M={M}, N={N}")
+    if K < 32 or K % 32:
+        raise ValueError(f"bf16 GEMM needs K % 32 == 0 and K >= 32, got K={K}")
+    if w.shape[1] != K:
+        raise ValueError(f"a is [{M}, {K}]: w must be [N, {K}], got "
+                         f"{tuple(w.shape)}")
+    if out is not None and (
+            out.dtype != torch.bfloat16 or out.device != a.device or
+            not out.is_contiguous() or tuple(out.shape) != (M, N)):
+        raise ValueError(f"out must be a contiguous bf16 [{M}, {N}] tensor "
+                         f"on {a.device}")
+    if a.is_cuda and (a.data_ptr() % 16 or w.data_ptr() % 16 or
+                      (out is not None and out.data_ptr() % 16)):
+        raise ValueError("a, w and out must be 16-byte aligned")
+    return M, N, K
+
+
+def gemm_bf16(a: torch.Tensor, w: torch.Tensor,
+              out: torch.Tensor = None) -> torch.Tensor:
+    """out[M,N] bf16 = a[M,K] @ w[N,K]^T for ANY M >= 1, fp32 accumulation,
+    one rounding: the entry point of the bf16 prefill.  On GPU M <= 64
+    runs skinny_gemm at pick_gemm_plan; larger M runs the output-tile
+    kernel gemm_bf16_tile_kernel (128 x 128 or 128 x 64 tiles, the
+    launcher's choice; LDS-DMA operands, v_mfma_f32_16x16x32_bf16).  No
+    split-K there: every output has one accumulator that takes the 32-k
+    blocks in ascending order, so the bits of out[m, n] depend on a[m, :],
+    w[n, :] and K alone, not on M, N or what else is in the call.  With
+    out given nothing is allocated at M > 64; no sync.  On CPU this is
+    torch.matmul(a, w.t())."""
+    M, N, K = _check_bf16_gemm_args(a, w, out)
+    if not a.is_cuda:
+        result = torch.matmul(a, w.t())
+        if out is not None:
+            out.copy_(result)
+            return out
+        return result
+    if M <= 64:
+        return skinny_gemm(a, w, out=out)
+    ops = _require_hip()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
+    ops.gemm_bf16_tile(out, a, w, 0)
+    return out
+
+
 FP8_MAX = 448.0  # OCP e4m3 max normal
 
 

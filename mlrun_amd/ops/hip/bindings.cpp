@@ -436,6 +436,31 @@ void gemm_fp8_tile(torch::Tensor out_bf16, torch::Tensor a8,
                        (int)M, (int)N, (int)K, (int)bn, stream());
 }
 
+// any-M bf16 GEMM on output tiles (prefill); bn 0 = the launcher's choice
+void gemm_bf16_tile(torch::Tensor out_bf16, torch::Tensor a, torch::Tensor w,
+                    int64_t bn) {
+  CHECK_DEV(out_bf16); CHECK_CONTIG(out_bf16); CHECK_BF16(out_bf16);
+  CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
+  CHECK_DEV(w); CHECK_CONTIG(w); CHECK_BF16(w);
+  TORCH_CHECK(a.dim() == 2 && w.dim() == 2, "a and w must be 2-d");
+  TORCH_CHECK(a.device() == out_bf16.device() && a.device() == w.device(),
+              "tensors on different devices");
+  int64_t M = a.size(0), K = a.size(1), N = w.size(0);
+  // grid.y = ceil(M / 128) must stay below 65536
+  TORCH_CHECK(M >= 1 && M <= 128 * 65535 && N >= 1 && N <= INT_MAX - 128 &&
+              K >= 32 && K % 32 == 0 && K <= INT_MAX - 128,
+              "bf16 tile path needs M, N >= 1 and K % 32 == 0");
+  TORCH_CHECK(w.size(1) == K, "a and w must agree on K");
+  TORCH_CHECK(out_bf16.numel() == M * N, "out must hold M * N elements");
+  TORCH_CHECK(bn == 0 || bn == 64 || bn == 128, "bn must be 0, 64 or 128");
+  TORCH_CHECK((uintptr_t)a.data_ptr() % 16 == 0 &&
+              (uintptr_t)w.data_ptr() % 16 == 0 &&
+              (uintptr_t)out_bf16.data_ptr() % 16 == 0,
+              "a, w and out must be 16-byte aligned");
+  launch_gemm_bf16_tile(out_bf16.data_ptr(), a.data_ptr(), w.data_ptr(),
+                        (int)M, (int)N, (int)K, (int)bn, stream());
+}
+
 void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
                     torch::Tensor a) {
   CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
@@ -1076,6 +1101,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "mxfp4-weight GEMM for any M on 128-row output tiles (prefill)");
   m.def("gemm_fp8_tile", &gemm_fp8_tile,
         "fp8 W8A8 GEMM for any M on 128-row output tiles (prefill)");
+  m.def("gemm_bf16_tile", &gemm_bf16_tile,
+        "bf16 GEMM for any M on 128-row output tiles (prefill)");
   m.def("quant_fp8_rows", &quant_fp8_rows,
         "dynamic per-row bf16 -> fp8 e4m3 quantization");
   m.def("attn_decode", &attn_decode, py::arg("o"), py::arg("q"),

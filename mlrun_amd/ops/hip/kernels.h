@@ -88,6 +88,12 @@ void launch_gemm_fp8_tile(void* out_bf16, const void* A8, const void* a_scale,
                           const void* W8, const void* w_scale, int M, int N,
                           int K, int bn, void* stream);
 
+// bf16 prefill GEMM (gemm_bf16_tile.hip): out[M,N] bf16 = A[M,K] . W[N,K]^T
+// with one fp32 accumulator per output and no split-K; any M, N >= 1,
+// K % 32 == 0; bn = 0 lets the launcher choose between 128 and 64
+void launch_gemm_bf16_tile(void* out_bf16, const void* A, const void* W,
+                           int M, int N, int K, int bn, void* stream);
+
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
                            int cols, void* stream);
 
