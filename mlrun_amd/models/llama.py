@@ -1629,6 +1629,33 @@ class LlamaDecodeEngine:
         return self._packed_pass(
             *self._check_packed(prompts, slots, starts), adapters)
 
+    @torch.no_grad()
+    def score_packed(self, prompts, slots, starts=None, adapters=None):
+        """prefill_packed that also scores the prompts: the same checks,
+        the same slot state (generation may continue from it) and the
+        same last-token logits, plus ``logprobs``, a list of n f32 device
+        tensors with ``logprobs[i][j]`` = log p(prompts[i][j + 1] |
+        everything before it), of length len(prompts[i]) - 1 (empty for a
+        one-token prompt).  Returns (logits, logprobs).
+
+        One ``ops.lm_head_logprobs`` runs over all T rows of the final
+        normed hidden state: the [T, vocab] logits are never stored.  It
+        reads the bf16 lm_head master, so the engine must be
+        weight_dtype="bf16" and tp_size 1; ``prefill_gemm`` may be
+        "library" or "bf16".  LoRA deltas apply to the four projections
+        as in prefill_packed."""
+        if self.weight_dtype != "bf16":
+            raise ValueError(
+                f'score_packed conflicts with weight_dtype='
+                f'"{self.weight_dtype}": it scores on the bf16 lm_head')
+        if self.tp_size != 1:
+            raise ValueError(
+                f"score_packed conflicts with tp_size={self.tp_size}: the "
+                "lm_head shards hold a part of the vocabulary each")
+        return self._packed_pass(
+            *self._check_packed(prompts, slots, starts), adapters,
+            score=True)
+
     def _check_packed(self, prompts, slots, starts=None):
         """The argument checks of a packed pass, all on the host and
         before any device work.  Returns (prompts, slots, starts) as
@@ -1668,14 +1695,15 @@ class LlamaDecodeEngine:
         return prompts, slot_list, start_list
 
     def _packed_pass(self, prompts, slot_list, start_list, adapters,
-                     whole=None):
+                     whole=None, score=False):
         """The packed pass over checked arguments (_check_packed).
         ``whole`` is None for a plain prefill_packed call, where a chunk
         with starts[i] > 0 continues a sequence and adds only its own
         tokens to the slot's token state.  prefill_cached passes the
         full prompts there: its chunks are the uncached ends of FRESH
         requests, whose every token, the cached ones too, counts as
-        in the prompt."""
+        in the prompt.  ``score`` (score_packed): also return the
+        log-probability of every chunk token but the first."""
         cfg, w = self.cfg, self.weights
         n = len(prompts)
         lens = [len(p) for p in prompts]
@@ -1723,6 +1751,16 @@ class LlamaDecodeEngine:
         else:
             prompt = (tok_slot.long(), tokens, kv_start == 0)
         self._first_tokens(logits, slots_long, prompt)
+        if score:
+            # row t's target is the next token of its chunk; a chunk's
+            # last row has none (-1) and is dropped from the result
+            targets = torch.tensor(
+                [t for p in prompts for t in p[1:] + [-1]],
+                dtype=torch.int32).to(self.device)
+            logprob, _ = ops.lm_head_logprobs(hidden.contiguous(),
+                                              w.lm_head, targets)
+            return logits, [logprob[a:a + length - 1] for a, length in
+                            zip(cu_list, lens)]
         return logits
 
     @torch.no_grad()
@@ -2521,7 +2559,7 @@ class LlamaServer:
             if taken:
                 self.engine_calls += 1
                 prompts, admit_slots, admit_ids = [], [], []
-                admit_params = []
+                admit_params, admit_score = [], []
                 for item, slot in zip(taken, free):
                     prompt, max_new, future = item[:3]
                     stream_q = item[3] if len(item) > 3 else None
@@ -2531,6 +2569,7 @@ class LlamaServer:
                     if by_request and params is None:
                         params = self._sampling_defaults
                     admit_params.append(params)
+                    admit_score.append(len(item) > 7 and bool(item[7]))
                     if engine.per_slot_temp:
                         engine.buf_temp[slot] = max(
                             float(temp or 0.0), 1e-4)
@@ -2573,12 +2612,25 @@ class LlamaServer:
                                                 dtype=torch.long)
                         admit = engine.prefill_cached if cached \
                             else engine.prefill_packed
+                        if any(admit_score):
+                            # "prompt_logprobs": the same pass, plus the
+                            # scores of its rows (do_event lets the field
+                            # through on packed, uncached servers only)
+                            admit = engine.score_packed
                         with stream_ctx():
                             if lora_on:
-                                admit(prompts, admit_slots,
-                                      adapters=admit_ids)
+                                admitted = admit(prompts, admit_slots,
+                                                 adapters=admit_ids)
                             else:
-                                admit(prompts, admit_slots)
+                                admitted = admit(prompts, admit_slots)
+                            for slot, want, scores in zip(
+                                    admit_slots, admit_score,
+                                    admitted[1] if any(admit_score)
+                                    else prompts):
+                                if want:  # read by do_event, next to
+                                    # the future's result
+                                    slots[slot]["future"].prompt_logprobs \
+                                        = scores.cpu().tolist()
                             out_ring[slot_ids, step % ring_len] = \
                                 engine.buf_tokens[slot_ids]
                             if by_request:
@@ -2745,6 +2797,7 @@ class LlamaServer:
         params = self._request_sampling(body, len(inputs))
         if params is not None:
             req_temp = None  # "temperature" is a SamplingParams field
+        score = self._request_prompt_logprobs(body, len(inputs))
         if self.scheduling == "continuous" and body.get("stream"):
             event.body = self._stream_generate(inputs, max_new, event,
                                                req_temp, adapter_id, params)
@@ -2755,9 +2808,13 @@ class LlamaServer:
                 future = concurrent.futures.Future()
                 self._tasks.put((prompt, max_new, future, None,
                                  req_temp, adapter_id,
-                                 params[j] if params else None))
+                                 params[j] if params else None)
+                                + ((score[j],) if score else ()))
                 futures.append(future)
             outputs = [f.result(timeout=600) for f in futures]
+            if score:
+                prompt_logprobs = [getattr(f, "prompt_logprobs", None)
+                                   for f in futures]
         elif self.batch_window_ms and len(inputs) < self.batch_size:
             outputs = self._batched_submit(inputs, max_new, adapter_id,
                                            params)
@@ -2781,12 +2838,52 @@ class LlamaServer:
             event.body["outputs"] = [row[0] for row in outputs]
             if body.get("logprobs"):
                 event.body["logprobs"] = [row[1] for row in outputs]
+        if score:
+            event.body["prompt_logprobs"] = prompt_logprobs
         if "retrieval" in body:  # RAG upstream step metadata
             event.body["retrieval"] = body["retrieval"]
         if self._model_logger:
             self._model_logger.push(start, {"inputs": [len(inputs)]},
                                     event.body)
         return event
+
+    def _request_prompt_logprobs(self, body: dict, n_prompts: int):
+        """The request's "prompt_logprobs" field as one flag per input,
+        or None when it is absent or false (nothing changes then).  True
+        asks for every input, a list of booleans for some of them.  Only
+        a continuous, packed, non-streaming server without a prefix cache
+        whose engine score_packed serves takes the field: anywhere else
+        it is a ValueError naming it, which fails this request alone."""
+        field = body.get("prompt_logprobs")
+        if not field:
+            return None
+        flags = [bool(f) for f in field] if isinstance(field, (list, tuple)) \
+            else [True] * n_prompts
+        if len(flags) != n_prompts:
+            raise ValueError(
+                f"prompt_logprobs lists {len(flags)} flags for "
+                f"{n_prompts} inputs")
+        if not any(flags):
+            return None
+        conflicts = [
+            what for what, bad in (
+                (f'scheduling="{self.scheduling}"',
+                 self.scheduling != "continuous"),
+                (f'prefill="{self.prefill}"', self.prefill != "packed"),
+                ('"stream": true', bool(body.get("stream"))),
+                ("prefix_cache_blocks > 0",
+                 self.engine.prefix_index is not None),
+                (f'weight_dtype="{self.weight_dtype}"',
+                 self.weight_dtype != "bf16"),
+                (f'kv_dtype="{self.kv_dtype}"', self.kv_dtype != "bf16"),
+                (f"tp_size={self.engine.tp_size}",
+                 self.engine.tp_size != 1)) if bad]
+        if conflicts:
+            raise ValueError(
+                "prompt_logprobs conflicts with " + ", ".join(conflicts)
+                + ': it needs scheduling="continuous", prefill="packed", '
+                "no streaming, no prefix cache and a bf16 engine")
+        return flags
 
     def _request_sampling(self, body: dict, n_prompts: int):
         """The request's sampling fields as one SamplingParams per

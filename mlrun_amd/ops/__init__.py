@@ -324,6 +324,73 @@ def gemm_bf16(a: torch.Tensor, w: torch.Tensor,
     return out
 
 
+def lm_head_logprobs_ws_numel(T: int, V: int) -> int:
+    """f32 elements of lm_head_logprobs' workspace for T rows and a
+    vocabulary of V: one (max, sum) pair per row and 64-column tile,
+    enough for either tile width."""
+    return 2 * T * ((V + 63) // 64)
+
+
+def lm_head_logprobs(h: torch.Tensor, w: torch.Tensor,
+                     targets: torch.Tensor, out: torch.Tensor = None,
+                     workspace: torch.Tensor = None, bn: int = 0):
+    """Prompt scoring: (logprob [T] f32, lse [T] f32) of targets [T] int32
+    under the logits z = bf16(h [T,K] @ w [V,K]^T), without materialising
+    them.  ``lse[t] = log sum_v exp(z[t, v])`` and ``logprob[t] = z[t,
+    targets[t]] - lse[t]``; a target outside [0, V) scores ``-lse[t]``.
+
+    On GPU every T >= 1 runs lm_head_logprobs_kernel: gemm_bf16_tile_kernel's
+    K loop, so z[t, v] is bit for bit what that kernel stores (one
+    accumulator, 32-k blocks in ascending k, one rounding), with an online
+    log-sum-exp and the target gather as the epilogue, and a fold kernel
+    over the ceil(V / BN) partials of a row.  No [T, V] buffer, no atomics.
+    ``out``: f32 [3, T], receives the rows logprob, lse and z_tgt (the
+    target logits, 0 where out of range); the two results are views of it.
+    ``workspace``: f32 of at least ``lm_head_logprobs_ws_numel(T, V)``
+    elements.  With both given nothing is allocated; no sync.  ``bn`` 64 /
+    128 forces the tile width, 0 lets the launcher choose.  ValueError
+    before any launch on a wrong argument.  The CPU branch is the
+    reference: fp32 matmul, one bf16 rounding, torch.logsumexp, gather."""
+    M, V, K = _check_bf16_gemm_args(h, w, None)
+    if targets.dtype != torch.int32 or tuple(targets.shape) != (M,) or \
+            targets.device != h.device or not targets.is_contiguous():
+        raise ValueError(f"targets must be a contiguous int32 [{M}] tensor "
+                         f"on {h.device}, got {tuple(targets.shape)} "
+                         f"{targets.dtype}")
+    if bn not in (0, 64, 128):
+        raise ValueError(f"bn must be 0, 64 or 128, got {bn}")
+    if out is not None and (
+            out.dtype != torch.float32 or out.device != h.device or
+            not out.is_contiguous() or tuple(out.shape) != (3, M)):
+        raise ValueError(f"out must be a contiguous f32 [3, {M}] tensor "
+                         f"on {h.device}")
+    need = lm_head_logprobs_ws_numel(M, V)
+    if workspace is not None and (
+            workspace.dtype != torch.float32 or
+            workspace.device != h.device or
+            not workspace.is_contiguous() or workspace.numel() < need or
+            workspace.data_ptr() % 8):
+        raise ValueError(f"workspace must be a contiguous 8-byte aligned "
+                         f"f32 tensor of at least {need} elements on "
+                         f"{h.device}")
+    if out is None:
+        out = torch.empty(3, M, dtype=torch.float32, device=h.device)
+    if not h.is_cuda:
+        z = (h.float() @ w.float().t()).to(torch.bfloat16).float()
+        idx = targets.long()
+        ok = (idx >= 0) & (idx < V)
+        out[1] = torch.logsumexp(z, dim=-1)
+        out[2] = torch.where(
+            ok, z.gather(1, idx.clamp(0, V - 1)[:, None])[:, 0], 0.0)
+        out[0] = out[2] - out[1]
+        return out[0], out[1]
+    ops = _require_hip()
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=h.device)
+    ops.lm_head_logprobs(out, workspace, h, w, targets, bn, 0)
+    return out[0], out[1]
+
+
 FP8_MAX = 448.0  # OCP e4m3 max normal
 
 

@@ -461,6 +461,51 @@ void gemm_bf16_tile(torch::Tensor out_bf16, torch::Tensor a, torch::Tensor w,
                         (int)M, (int)N, (int)K, (int)bn, stream());
 }
 
+// prompt scoring: out f32 [3, T] = (logprob, lse, z_tgt) rows; ws f32 of at
+// least 2 * lm_head_logprobs_ws_pairs(T, V) elements
+int64_t lm_head_logprobs_ws_numel(int64_t T, int64_t V) {
+  TORCH_CHECK(T >= 1 && T <= 128 * 65535 && V >= 1 && V <= INT_MAX - 128,
+              "lm_head_logprobs needs T, V >= 1");
+  return 2 * lm_head_logprobs_ws_pairs((int)T, (int)V);
+}
+
+void lm_head_logprobs(torch::Tensor out, torch::Tensor ws, torch::Tensor h,
+                      torch::Tensor w, torch::Tensor targets, int64_t bn,
+                      int64_t order) {
+  CHECK_DEV(out); CHECK_CONTIG(out); CHECK_F32(out);
+  CHECK_DEV(ws); CHECK_CONTIG(ws); CHECK_F32(ws);
+  CHECK_DEV(h); CHECK_CONTIG(h); CHECK_BF16(h);
+  CHECK_DEV(w); CHECK_CONTIG(w); CHECK_BF16(w);
+  CHECK_DEV(targets); CHECK_CONTIG(targets); CHECK_I32(targets);
+  TORCH_CHECK(h.dim() == 2 && w.dim() == 2, "h and w must be 2-d");
+  TORCH_CHECK(h.device() == out.device() && h.device() == w.device() &&
+              h.device() == ws.device() && h.device() == targets.device(),
+              "tensors on different devices");
+  int64_t T = h.size(0), K = h.size(1), V = w.size(0);
+  TORCH_CHECK(T >= 1 && T <= 128 * 65535 && V >= 1 && V <= INT_MAX - 128 &&
+              K >= 32 && K % 32 == 0 && K <= INT_MAX - 128,
+              "lm_head_logprobs needs T, V >= 1 and K % 32 == 0");
+  // the grid is one-dimensional: tiles of 128 rows x 64 columns at most
+  TORCH_CHECK(((T + 127) / 128) * ((V + 63) / 64) <= INT_MAX,
+              "too many tiles");
+  TORCH_CHECK(w.size(1) == K, "h and w must agree on K");
+  TORCH_CHECK(targets.dim() == 1 && targets.numel() == T,
+              "targets must be int32 [T]");
+  TORCH_CHECK(out.numel() == 3 * T, "out must hold 3 * T elements");
+  TORCH_CHECK(ws.numel() >= lm_head_logprobs_ws_numel(T, V),
+              "workspace too small");
+  TORCH_CHECK(bn == 0 || bn == 64 || bn == 128, "bn must be 0, 64 or 128");
+  TORCH_CHECK(order == 0 || order == 1, "order must be 0 or 1");
+  TORCH_CHECK((uintptr_t)h.data_ptr() % 16 == 0 &&
+              (uintptr_t)w.data_ptr() % 16 == 0 &&
+              (uintptr_t)ws.data_ptr() % 8 == 0,
+              "h and w must be 16-byte and ws 8-byte aligned");
+  float* o = out.data_ptr<float>();
+  launch_lm_head_logprobs(o, o + T, o + 2 * T, ws.data_ptr(), h.data_ptr(),
+                          w.data_ptr(), targets.data_ptr(), (int)T, (int)V,
+                          (int)K, (int)bn, (int)order, stream());
+}
+
 void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
                     torch::Tensor a) {
   CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
@@ -1103,6 +1148,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp8 W8A8 GEMM for any M on 128-row output tiles (prefill)");
   m.def("gemm_bf16_tile", &gemm_bf16_tile,
         "bf16 GEMM for any M on 128-row output tiles (prefill)");
+  m.def("lm_head_logprobs", &lm_head_logprobs, py::arg("out"), py::arg("ws"),
+        py::arg("h"), py::arg("w"), py::arg("targets"), py::arg("bn") = 0,
+        py::arg("order") = 0,
+        "prompt scoring: lm_head GEMM with a fused log-sum-exp and gather");
+  m.def("lm_head_logprobs_ws_numel", &lm_head_logprobs_ws_numel,
+        "f32 elements of lm_head_logprobs' workspace");
   m.def("quant_fp8_rows", &quant_fp8_rows,
         "dynamic per-row bf16 -> fp8 e4m3 quantization");
   m.def("attn_decode", &attn_decode, py::arg("o"), py::arg("q"),

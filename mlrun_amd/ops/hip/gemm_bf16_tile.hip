@@ -74,79 +74,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "bf16_tile_loop.h"  // helpers shared with lm_head_logprobs.hip
 #include "kernels.h"
-
-typedef __attribute__((ext_vector_type(4))) float b16t_f32x4;
-typedef __attribute__((ext_vector_type(8))) short b16t_bf16x8;
-
-#define B16T_DEV __device__ __attribute__((always_inline)) inline
-
-#define B16T_BM 128   // rows of a workgroup tile
-#define B16T_ROW 128  // bytes of a row per stage (64 k)
-
-typedef __attribute__((address_space(3))) void* b16t_lds_ptr;
-
-B16T_DEV unsigned short b16t_f2bf(float f) {  // round-to-nearest-even
-  union { float f; uint32_t i; } v;
-  v.f = f;
-  return (unsigned short)((v.i + 0x7fffu + ((v.i >> 16) & 1u)) >> 16);
-}
-
-B16T_DEV void b16t_barrier() {  // __syncthreads()
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
-}
-
-B16T_DEV void b16t_wait_dma() {  // every LDS-DMA of this wave has landed
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// One stage of a wave: KSTEPS (2, or 1 in the 32-k tail) k-steps, each 16
-// bytes of each of its 4 x 16 activation rows and NI x 16 weight rows, then
-// 4 x NI MFMAs.  ap / wp point at this lane's row of the first sub-tile;
-// x[s] is the byte offset of its (swizzled) chunk of k-step s.
-template <int NI, int KSTEPS>
-B16T_DEV void b16t_stage(b16t_f32x4 (&acc)[4][NI], const unsigned char* ap,
-                         const unsigned char* wp, const int (&x)[2]) {
-  b16t_bf16x8 af[KSTEPS][4], wf[KSTEPS][NI];
-#pragma unroll
-  for (int s = 0; s < KSTEPS; ++s) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      af[s][j] = *reinterpret_cast<const b16t_bf16x8*>(
-          ap + j * 16 * B16T_ROW + x[s]);
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      wf[s][i] = *reinterpret_cast<const b16t_bf16x8*>(
-          wp + i * 16 * B16T_ROW + x[s]);
-  }
-  // (the host pass cannot type-check the MFMA builtin)
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-  for (int s = 0; s < KSTEPS; ++s)  // ascending k: the summation order
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            wf[s][i], af[s][j], acc[j][i], 0, 0, 0);
-#endif
-}
 
 template <int BN>
 __global__ __launch_bounds__(256) void gemm_bf16_tile_kernel(
     unsigned short* __restrict__ C, const unsigned char* __restrict__ A,
     const unsigned char* __restrict__ W, int M, int N, int K) {
-  constexpr int NI = BN / 32;              // 16-wide n sub-tiles of a wave
-  constexpr int A_B = B16T_BM * B16T_ROW;  // bytes of the A tile of a stage
-  constexpr int STAGE_B = A_B + BN * B16T_ROW;
-  constexpr int NDMA_A = B16T_BM / 32;     // DMA instructions of a wave
-  constexpr int NDMA_W = BN / 32;
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * STAGE_B];
-
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -157,84 +91,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_tile_kernel(
   const int wm0 = m0 + (wave >> 1) * 64;  // this wave's sub-tile
   const int wn0 = n0 + (wave & 1) * (BN / 2);
   const bool active = wm0 < M && wn0 < N;  // wave-uniform
-  const size_t row_b = (size_t)K * 2;      // bytes of an operand row
-
-  // --- DMA of one wave: instruction i covers the 8 tile rows
-  // 8 * (NDMA * wave + i) ..; lane l writes LDS chunk position l & 7 of
-  // row l >> 3 and fetches source chunk (l & 7) ^ swz(row) for it
-  const unsigned char* asrc[NDMA_A];
-  const unsigned char* wsrc[NDMA_W];
-  int acol[NDMA_A], wcol[NDMA_W];
-#pragma unroll
-  for (int i = 0; i < NDMA_A; ++i) {
-    const int row = 8 * (NDMA_A * wave + i) + (lane >> 3);
-    acol[i] = (((lane & 7) ^ (row >> 1)) & 7) * 16;
-    asrc[i] = A + (size_t)min(m0 + row, M - 1) * row_b;
-  }
-#pragma unroll
-  for (int i = 0; i < NDMA_W; ++i) {
-    const int row = 8 * (NDMA_W * wave + i) + (lane >> 3);
-    wcol[i] = (((lane & 7) ^ (row >> 1)) & 7) * 16;
-    wsrc[i] = W + (size_t)min(n0 + row, N - 1) * row_b;
-  }
-  const int nfull = K >> 6;          // 64-k stages
-  const bool tail = (K & 32) != 0;   // plus one of 32 k
-  const int nstages = nfull + (tail ? 1 : 0);
-  // stage s -> buffer `buf`.  A full stage masks its column with 127; the
-  // 64-byte tail stage (s == nfull) with 63, which keeps its lanes inside
-  // the row's last 64 bytes
-  auto issue = [&](int s, int buf) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const size_t k0 = (size_t)s * B16T_ROW;
-    const int colmask = s == nfull ? 63 : 127;
-    unsigned char* dst = lds + buf * STAGE_B;
-#pragma unroll
-    for (int i = 0; i < NDMA_A; ++i)
-      __builtin_amdgcn_global_load_lds(
-          asrc[i] + k0 + (acol[i] & colmask),
-          (b16t_lds_ptr)(dst + (NDMA_A * wave + i) * 1024), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < NDMA_W; ++i)
-      __builtin_amdgcn_global_load_lds(
-          wsrc[i] + k0 + (wcol[i] & colmask),
-          (b16t_lds_ptr)(dst + A_B + (NDMA_W * wave + i) * 1024), 16, 0, 0);
-#else
-    (void)s; (void)buf;
-#endif
-  };
-
-  b16t_f32x4 acc[4][NI];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < NI; ++i) acc[j][i] = b16t_f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // fragment rows of this lane: row lq of each 16-row sub-tile, source
-  // chunk 4 s + lh in k-step s (sub-tile bases are multiples of 16, so the
-  // swizzle of the row is that of lq)
-  const int swz = (lq >> 1) & 7;
-  const int x[2] = {(lh ^ swz) * 16, ((4 + lh) ^ swz) * 16};
-  const int aoff = ((wave >> 1) * 64 + lq) * B16T_ROW;
-  const int woff = A_B + ((wave & 1) * (BN / 2) + lq) * B16T_ROW;
-
-  issue(0, 0);
-  int buf = 0;  // buffer of stage t
-  for (int t = 0; t < nfull; ++t) {
-    b16t_wait_dma();
-    b16t_barrier();
-    if (t + 1 < nstages) issue(t + 1, buf ^ 1);
-    if (active)
-      b16t_stage<NI, 2>(acc, lds + buf * STAGE_B + aoff,
-                        lds + buf * STAGE_B + woff, x);
-    buf ^= 1;
-  }
-  if (tail) {
-    b16t_wait_dma();
-    b16t_barrier();
-    if (active)
-      b16t_stage<NI, 1>(acc, lds + buf * STAGE_B + aoff,
-                        lds + buf * STAGE_B + woff, x);
-  }
+#include "bf16_tile_kloop.inc"  // the K loop: declares lds and acc
 
   // --- epilogue: acc[j][i][r] = C[wm0 + 16 j + lq][wn0 + 16 i + 4 lh + r]
   if (!active) return;

@@ -94,6 +94,18 @@ void launch_gemm_fp8_tile(void* out_bf16, const void* A8, const void* a_scale,
 void launch_gemm_bf16_tile(void* out_bf16, const void* A, const void* W,
                            int M, int N, int K, int bn, void* stream);
 
+// prompt scoring (lm_head_logprobs.hip): for h[T,K], w[V,K] bf16 and
+// targets[T] int32, z_tgt[t] = the bf16 logit gemm_bf16_tile would store at
+// [t, targets[t]] (0 if out of [0, V)), lse[t] = log sum exp of row t's
+// logits, logprob = z_tgt - lse; all f32 [T].  ws holds at least
+// lm_head_logprobs_ws_pairs(T, V) 8-byte (max, sum) pairs.  K % 32 == 0;
+// bn as above; order 0 = M tiles fastest (default), 1 = column tiles fastest
+long long lm_head_logprobs_ws_pairs(int T, int V);
+void launch_lm_head_logprobs(void* logprob, void* lse, void* z_tgt, void* ws,
+                             const void* h, const void* w,
+                             const void* targets, int T, int V, int K, int bn,
+                             int order, void* stream);
+
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
                            int cols, void* stream);
 
