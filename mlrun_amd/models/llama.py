@@ -448,23 +448,23 @@ class LlamaDecodeEngine:
                  prefix_cache_blocks: int = 0,
                  prefill_gemm: str = "library",
                  lora_prefill: str = "library"):
-        if prefill_gemm not in ("library", "mxfp4", "fp8", "bf16"):
+        if prefill_gemm not in ("library", "mxfp4", "mxfp4a8", "fp8", "bf16"):
             raise ValueError(f"unknown prefill_gemm {prefill_gemm!r} "
-                             "(expected 'library', 'mxfp4', 'fp8' or "
-                             "'bf16')")
+                             "(expected 'library', 'mxfp4', 'mxfp4a8', "
+                             "'fp8' or 'bf16')")
         if lora_prefill not in ("library", "sgmv"):
             raise ValueError(f"unknown lora_prefill {lora_prefill!r} "
                              "(expected 'library' or 'sgmv')")
         device_type = torch.device(
             device or ("cuda:0" if torch.cuda.is_available() else "cpu")).type
-        if prefill_gemm == "mxfp4" and not (
+        if prefill_gemm in ("mxfp4", "mxfp4a8") and not (
                 weight_dtype == "mxfp4w" and device_type == "cuda"
                 and tp_size == 1):
             raise ValueError(
-                f'prefill_gemm="mxfp4" needs weight_dtype="mxfp4w" on one '
-                f"GPU, got weight_dtype={weight_dtype!r} on {device_type} "
-                f"with tp_size={tp_size}: there are no mxfp4 packs to run "
-                "on")
+                f'prefill_gemm="{prefill_gemm}" needs weight_dtype="mxfp4w" '
+                f"on one GPU, got weight_dtype={weight_dtype!r} on "
+                f"{device_type} with tp_size={tp_size}: there are no mxfp4 "
+                "packs to run on")
         if prefill_gemm == "fp8" and not (
                 weight_dtype == "fp8w" and device_type == "cuda"
                 and tp_size == 1):
@@ -630,7 +630,8 @@ class LlamaDecodeEngine:
         # "library": the prefills multiply by the bf16 masters (hipBLASLt);
         # "mxfp4" / "fp8": they run ops.gemm_mxfp4 / ops.gemm_fp8 on the
         # packs the decode step reads, so one model serves both phases
-        # and the masters can go (release_master_weights)
+        # and the masters can go (release_master_weights); "mxfp4a8": the
+        # mxfp4 packs again, against e4m3 activations (ops.gemm_mxfp4_a8)
         self.prefill_gemm = prefill_gemm
         # fill-based (ns4 at B=32): the graph bakes ONE nsplit for all
         # context lengths, and decode mostly runs at S << max_seq_len —
@@ -1376,17 +1377,18 @@ class LlamaDecodeEngine:
     def release_master_weights(self):
         """Free the bf16 wqkv / wo / wgu / wdown of every layer and
         lm_head (embedding and norm weights stay): with
-        ``prefill_gemm="mxfp4"`` / ``"fp8"`` prefill and decode both run
-        on the packs, so an mxfp4w engine then holds 4.25 bits per weight
+        ``prefill_gemm="mxfp4"`` / ``"mxfp4a8"`` / ``"fp8"`` prefill and
+        decode both run on the packs, so an mxfp4w engine then holds 4.25 bits per weight
         and an fp8w engine 8 bits plus one f32 scale per row.
         Engines that share these weights and packs (replicas) keep
         working, and so do adapters under either ``lora_prefill``: the
         LoRA tables are no masters and stay.  Afterwards
         rebuild_weight_packs() / rebuild_fp8_packs(), weights.state_dict()
         and weights.load_state_dict() raise ValueError."""
-        if self.prefill_gemm not in ("mxfp4", "fp8"):
+        if self.prefill_gemm not in ("mxfp4", "mxfp4a8", "fp8"):
             raise ValueError(
-                "release_master_weights() needs prefill_gemm=\"mxfp4\" or "
+                "release_master_weights() needs prefill_gemm=\"mxfp4\", "
+                "\"mxfp4a8\" or "
                 f"\"fp8\", got prefill_gemm={self.prefill_gemm!r}: the "
                 "library prefill reads the bf16 masters")
         w = self.weights
@@ -1448,9 +1450,9 @@ class LlamaDecodeEngine:
     def _prefill_project(self, plan):
         """_run_layers' ``project`` of the prefills: the library GEMM
         on the masters (or ops.gemm_bf16 on them under
-        ``prefill_gemm="bf16"``), or ops.gemm_mxfp4 / ops.gemm_fp8 on the
-        packs under ``prefill_gemm="mxfp4"`` / ``"fp8"``, plus the LoRA
-        deltas of ``plan``."""
+        ``prefill_gemm="bf16"``), or ops.gemm_mxfp4 / ops.gemm_mxfp4_a8 /
+        ops.gemm_fp8 on the packs under ``prefill_gemm="mxfp4"`` /
+        ``"mxfp4a8"`` / ``"fp8"``, plus the LoRA deltas of ``plan``."""
         layers = self.weights.layers
         if self.prefill_gemm == "fp8":
             def project(li, name, x):
@@ -1461,6 +1463,11 @@ class LlamaDecodeEngine:
             def project(li, name, x):
                 return self._lora_prefill(plan, li, name, x, ops.gemm_mxfp4(
                     x.contiguous(), *self._mx4_packs[(li, name)]))
+            return project
+        if self.prefill_gemm == "mxfp4a8":
+            def project(li, name, x):
+                return self._lora_prefill(plan, li, name, x, self._mx4a8_rows(
+                    x, self._mx4_packs[(li, name)]))
             return project
         if self.prefill_gemm == "bf16":
             def project(li, name, x):
@@ -1479,8 +1486,17 @@ class LlamaDecodeEngine:
         a8, a_scale = ops.quant_fp8_rows(x.contiguous())
         return ops.gemm_fp8(a8, a_scale, *pack)
 
+    def _mx4a8_rows(self, x, pack):
+        """x [T, K] bf16 times an mxfp4 pack on the block-scaled MFMA:
+        per-row dynamic e4m3 codes in natural k order, then the W4A8
+        GEMM."""
+        a8, a_scale = ops.quant_fp8_rows(x.contiguous(), swizzle=False)
+        return ops.gemm_mxfp4_a8(a8, a_scale, *pack)
+
     def _prefill_logits(self, last):
         """Logits of the prefills' last-token rows ``last`` [n, H]."""
+        if self.prefill_gemm == "mxfp4a8":
+            return self._mx4a8_rows(last, self._mx4_packs["lm_head"])
         if self.prefill_gemm == "fp8":
             return self._fp8_rows(last, self._fp8_packs["lm_head"])
         if self.prefill_gemm == "mxfp4":
@@ -2113,7 +2129,12 @@ class LlamaServer:
     - ``prefill_gemm``: "library" (default) prefills on the bf16 master
       weights; "mxfp4" (needs ``weight_dtype="mxfp4w"``) prefills with
       ``ops.gemm_mxfp4`` on the packs the decode step reads, so prompt
-      and generated tokens come from one model; "fp8" (needs
+      and generated tokens come from one model; "mxfp4a8" (same
+      requirement) runs the same packs on the block-scaled MFMA with
+      ``ops.quant_fp8_rows(swizzle=False)`` + ``ops.gemm_mxfp4_a8``:
+      prompt rows then see e4m3 activations and generated rows (the
+      W4A16 decode step) do not, as "library" on an fp8w engine mixes
+      two models; "fp8" (needs
       ``weight_dtype="fp8w"``) does the same for the fp8 packs with
       ``ops.quant_fp8_rows`` + ``ops.gemm_fp8``; "bf16" (needs
       ``weight_dtype="bf16"``) keeps the bf16 weights and runs the
@@ -2121,7 +2142,8 @@ class LlamaServer:
       tile kernel sums every output in one fixed order whatever the
       request is packed with (slower than the library; see
       docs/kernels.md).  ``release_masters=True``
-      (needs ``prefill_gemm="mxfp4"`` or ``"fp8"``) then frees the bf16
+      (needs ``prefill_gemm="mxfp4"``, ``"mxfp4a8"`` or ``"fp8"``) then
+      frees the bf16
       projection weights and lm_head once the checkpoint is loaded and
       packed: the deployment holds 4.25 (mxfp4w) or 8 (fp8w) bits per
       weight.
@@ -2325,9 +2347,10 @@ class LlamaServer:
                 'attention kernel does not read fp8 caches): use '
                 'kv_dtype="bf16" or prefill="exact"')
         if self.release_masters and \
-                self.prefill_gemm not in ("mxfp4", "fp8"):
+                self.prefill_gemm not in ("mxfp4", "mxfp4a8", "fp8"):
             raise ValueError(
-                "release_masters=True needs prefill_gemm=\"mxfp4\" or "
+                "release_masters=True needs prefill_gemm=\"mxfp4\", "
+                "\"mxfp4a8\" or "
                 f"\"fp8\", got prefill_gemm={self.prefill_gemm!r}: the "
                 "library prefill reads the bf16 masters")
         if not torch.cuda.is_available():

@@ -420,8 +420,11 @@ def quantize_fp8_weight(w: torch.Tensor):
 
 
 def quant_fp8_rows(a: torch.Tensor, a8: torch.Tensor = None,
-                   a_scale: torch.Tensor = None):
-    """Dynamic per-row activation quantization to fp8 e4m3."""
+                   a_scale: torch.Tensor = None, swizzle: bool = True):
+    """Dynamic per-row activation quantization to fp8 e4m3.  The codes
+    come in the fp8 GEMMs' pair-swizzled k order; swizzle=False gives
+    the same codes (and scales) in natural k order, what gemm_mxfp4_a8
+    reads."""
     rows, cols = a.shape[0], a.shape[-1]
     if a.is_cuda:
         ops = _require_hip()
@@ -430,12 +433,14 @@ def quant_fp8_rows(a: torch.Tensor, a8: torch.Tensor = None,
         if a_scale is None:
             a_scale = torch.empty(rows, dtype=torch.float32,
                                   device=a.device)
-        ops.quant_fp8_rows(a8, a_scale, a)
+        ops.quant_fp8_rows(a8, a_scale, a, bool(swizzle))
         return a8, a_scale
     amax = a.float().abs().amax(dim=-1).clamp(min=1e-8)
     scale = amax / FP8_MAX
     q = (a.float() / scale[:, None]).to(torch.float8_e4m3fn)
-    q = _fp8_pair_swizzle(q.view(torch.uint8))
+    q = q.view(torch.uint8)
+    if swizzle:
+        q = _fp8_pair_swizzle(q)
     if a8 is not None:
         a8.copy_(q)
         a_scale.copy_(scale)
@@ -721,6 +726,76 @@ def gemm_mxfp4(a: torch.Tensor, w4: torch.Tensor, w_scale: torch.Tensor,
     elif out.data_ptr() % 16:      # the tile kernel stores 8-byte words
         raise ValueError("out must be 16-byte aligned")
     ops.gemm_mxfp4_tile(out, a, w4, w_scale, 0)
+    return out
+
+
+def _check_mxfp4_a8_gemm_args(a8, a_scale, w4, w_scale, out):
+    """The argument checks of gemm_mxfp4_a8: those of the mxfp4 pack
+    (_check_mxfp4_gemm_args) and of the fp8 activations
+    (_check_fp8_gemm_args); ValueError before any launch.  Returns
+    M, N, K."""
+    for name, t, dtype, rank in (("a8", a8, torch.uint8, 2),
+                                 ("a_scale", a_scale, torch.float32, 1),
+                                 ("w4", w4, torch.uint8, 2),
+                                 ("w_scale", w_scale, torch.uint8, 2)):
+        if t.dim() != rank or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {rank}-d {dtype} "
+                             f"tensor, got {tuple(t.shape)} {t.dtype}")
+        if t.device != a8.device:
+            raise ValueError(f"{name} is on {t.device}, a8 on {a8.device}")
+    M, K = a8.shape
+    N = w4.shape[0]
+    _check_mxfp4_k(K)
+    if M < 1 or N < 1:
+        raise ValueError(f"mxfp4a8 GEMM needs M, N >= 1, got M={M}, N={N}")
+    if w4.shape[1] != K // 2 or tuple(w_scale.shape) != (N, K // 32):
+        raise ValueError(
+            f"a8 is [{M}, {K}]: w4 must be [N, {K // 2}] and w_scale "
+            f"[N, {K // 32}], got {tuple(w4.shape)} / {tuple(w_scale.shape)}")
+    if a_scale.numel() != M:
+        raise ValueError(f"a_scale must hold M={M} scales, got "
+                         f"{a_scale.numel()}")
+    if out is not None and (
+            out.dtype != torch.bfloat16 or out.device != a8.device or
+            not out.is_contiguous() or tuple(out.shape) != (M, N)):
+        raise ValueError(f"out must be a contiguous bf16 [{M}, {N}] tensor "
+                         f"on {a8.device}")
+    # the kernel reads four scale bytes of a row as one dword
+    if a8.is_cuda and (a8.data_ptr() % 16 or w4.data_ptr() % 16 or
+                       w_scale.data_ptr() % 4 or
+                       (out is not None and out.data_ptr() % 16)):
+        raise ValueError("a8, w4 and out must be 16-byte and w_scale "
+                         "4-byte aligned")
+    return M, N, K
+
+
+def gemm_mxfp4_a8(a8: torch.Tensor, a_scale: torch.Tensor, w4: torch.Tensor,
+                  w_scale: torch.Tensor,
+                  out: torch.Tensor = None) -> torch.Tensor:
+    """out[M,N] bf16 = a_scale[m] * (e4m3(a8) @ dequant(w4, w_scale)^T)[m, n]
+    for ANY M >= 1: the W4A8 entry point of the mxfp4 prefill.  a8 /
+    a_scale are the codes of quant_fp8_rows(swizzle=False), NATURAL k
+    order; w4 / w_scale a pack of quantize_mxfp4_weight, as it is.  On
+    GPU every M runs gemm_mxfp4_a8_tile_kernel (128 x 128 or 128 x 64
+    tiles, the launcher's choice): LDS-DMA operands and the block-scaled
+    128-k MFMA with the fp4 codes and E8M0 scales as operands, nothing
+    converted.  No split-K: one summation order whatever the grid.  With
+    out given nothing is allocated; no sync.  The CPU branch is the
+    reference: the fp32 product of the dequantized operands, rounded
+    once."""
+    M, N, K = _check_mxfp4_a8_gemm_args(a8, a_scale, w4, w_scale, out)
+    if not a8.is_cuda:
+        a = a8.view(torch.float8_e4m3fn).float() * a_scale[:, None]
+        w = dequantize_mxfp4_weight(w4, w_scale)
+        result = (a @ w.float().t()).to(torch.bfloat16)
+        if out is not None:
+            out.copy_(result)
+            return out
+        return result
+    ops = _require_hip()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a8.device)
+    ops.gemm_mxfp4_a8_tile(out, a8, a_scale, w4, w_scale, 0)
     return out
 
 

@@ -436,6 +436,44 @@ void gemm_fp8_tile(torch::Tensor out_bf16, torch::Tensor a8,
                        (int)M, (int)N, (int)K, (int)bn, stream());
 }
 
+// any-M W4A8 GEMM on output tiles (prefill): e4m3 activations in natural k
+// order x an mxfp4 pack; bn 0 = the launcher's choice
+void gemm_mxfp4_a8_tile(torch::Tensor out_bf16, torch::Tensor a8,
+                        torch::Tensor a_scale, torch::Tensor w4,
+                        torch::Tensor w_scale, int64_t bn) {
+  CHECK_DEV(out_bf16); CHECK_CONTIG(out_bf16); CHECK_BF16(out_bf16);
+  CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
+  CHECK_DEV(a_scale); CHECK_CONTIG(a_scale); CHECK_F32(a_scale);
+  CHECK_DEV(w4); CHECK_CONTIG(w4); CHECK_U8(w4);
+  CHECK_DEV(w_scale); CHECK_CONTIG(w_scale); CHECK_U8(w_scale);
+  TORCH_CHECK(a8.dim() == 2 && w4.dim() == 2 && w_scale.dim() == 2,
+              "a8, w4 and w_scale must be 2-d");
+  TORCH_CHECK(a8.device() == out_bf16.device() &&
+              a8.device() == a_scale.device() &&
+              a8.device() == w4.device() && a8.device() == w_scale.device(),
+              "tensors on different devices");
+  int64_t M = a8.size(0), K = a8.size(1), N = w4.size(0);
+  // grid.y = ceil(M / 128) must stay below 65536
+  TORCH_CHECK(M >= 1 && M <= 128 * 65535 && N >= 1 && N <= INT_MAX - 128 &&
+              K >= 128 && K % 128 == 0 && K <= INT_MAX - 128,
+              "mxfp4a8 tile path needs M, N >= 1 and K % 128 == 0");
+  TORCH_CHECK(w4.size(1) == K / 2 && w_scale.size(0) == N &&
+              w_scale.size(1) == K / 32, "w4 / w_scale shape mismatch");
+  TORCH_CHECK(a_scale.numel() == M, "a_scale must have M elements");
+  TORCH_CHECK(out_bf16.numel() == M * N, "out must hold M * N elements");
+  TORCH_CHECK(bn == 0 || bn == 64 || bn == 128, "bn must be 0, 64 or 128");
+  // the kernel loads four scale bytes of a row as one dword
+  TORCH_CHECK((uintptr_t)a8.data_ptr() % 16 == 0 &&
+              (uintptr_t)w4.data_ptr() % 16 == 0 &&
+              (uintptr_t)out_bf16.data_ptr() % 16 == 0 &&
+              (uintptr_t)w_scale.data_ptr() % 4 == 0,
+              "a8, w4 and out must be 16-byte, w_scale 4-byte aligned");
+  launch_gemm_mxfp4_a8_tile(out_bf16.data_ptr(), a8.data_ptr(),
+                            a_scale.data_ptr(), w4.data_ptr(),
+                            w_scale.data_ptr(), (int)M, (int)N, (int)K,
+                            (int)bn, stream());
+}
+
 // any-M bf16 GEMM on output tiles (prefill); bn 0 = the launcher's choice
 void gemm_bf16_tile(torch::Tensor out_bf16, torch::Tensor a, torch::Tensor w,
                     int64_t bn) {
@@ -507,7 +545,7 @@ void lm_head_logprobs(torch::Tensor out, torch::Tensor ws, torch::Tensor h,
 }
 
 void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
-                    torch::Tensor a) {
+                    torch::Tensor a, bool swizzle) {
   CHECK_DEV(a8); CHECK_CONTIG(a8); CHECK_U8(a8);
   CHECK_DEV(a_scale); CHECK_F32(a_scale);
   CHECK_DEV(a); CHECK_CONTIG(a); CHECK_BF16(a);
@@ -517,7 +555,7 @@ void quant_fp8_rows(torch::Tensor a8, torch::Tensor a_scale,
   TORCH_CHECK(a8.numel() == a.numel() && a_scale.numel() >= rows,
               "size mismatch");
   launch_quant_fp8_rows(a8.data_ptr(), a_scale.data_ptr(), a.data_ptr(),
-                        (int)rows, (int)cols, stream());
+                        (int)rows, (int)cols, swizzle, stream());
 }
 
 void cast_f32_bf16(torch::Tensor out, torch::Tensor in) {
@@ -1146,6 +1184,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "mxfp4-weight GEMM for any M on 128-row output tiles (prefill)");
   m.def("gemm_fp8_tile", &gemm_fp8_tile,
         "fp8 W8A8 GEMM for any M on 128-row output tiles (prefill)");
+  m.def("gemm_mxfp4_a8_tile", &gemm_mxfp4_a8_tile,
+        "mxfp4-weight x e4m3-activation GEMM on the block-scaled MFMA "
+        "for any M on 128-row output tiles (prefill)");
   m.def("gemm_bf16_tile", &gemm_bf16_tile,
         "bf16 GEMM for any M on 128-row output tiles (prefill)");
   m.def("lm_head_logprobs", &lm_head_logprobs, py::arg("out"), py::arg("ws"),
@@ -1154,7 +1195,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "prompt scoring: lm_head GEMM with a fused log-sum-exp and gather");
   m.def("lm_head_logprobs_ws_numel", &lm_head_logprobs_ws_numel,
         "f32 elements of lm_head_logprobs' workspace");
-  m.def("quant_fp8_rows", &quant_fp8_rows,
+  m.def("quant_fp8_rows", &quant_fp8_rows, py::arg("a8"), py::arg("a_scale"),
+        py::arg("a"), py::arg("swizzle") = true,
         "dynamic per-row bf16 -> fp8 e4m3 quantization");
   m.def("attn_decode", &attn_decode, py::arg("o"), py::arg("q"),
         py::arg("kc"), py::arg("vc"), py::arg("seq_lens"),

@@ -88,6 +88,15 @@ void launch_gemm_fp8_tile(void* out_bf16, const void* A8, const void* a_scale,
                           const void* W8, const void* w_scale, int M, int N,
                           int K, int bn, void* stream);
 
+// W4A8 prefill GEMM (gemm_mxfp4_a8_tile.hip): out[M,N] bf16 = a_scale[m] *
+// (A8 . dequant(W4, w_scale)^T) on the block-scaled MFMA; A8 holds e4m3
+// codes in NATURAL k order, W4 / w_scale are a pack as above; any M, N >=
+// 1, K % 128 == 0; bn = 0 lets the launcher choose between 128 and 64
+void launch_gemm_mxfp4_a8_tile(void* out_bf16, const void* A8,
+                               const void* a_scale, const void* W4,
+                               const void* w_scale, int M, int N, int K,
+                               int bn, void* stream);
+
 // bf16 prefill GEMM (gemm_bf16_tile.hip): out[M,N] bf16 = A[M,K] . W[N,K]^T
 // with one fp32 accumulator per output and no split-K; any M, N >= 1,
 // K % 32 == 0; bn = 0 lets the launcher choose between 128 and 64
@@ -106,8 +115,9 @@ void launch_lm_head_logprobs(void* logprob, void* lse, void* z_tgt, void* ws,
                              const void* targets, int T, int V, int K, int bn,
                              int order, void* stream);
 
+// swizzle: the fp8 GEMMs' pair-swizzled k order; false = natural order
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
-                           int cols, void* stream);
+                           int cols, bool swizzle, void* stream);
 
 void launch_cast_f32_bf16(void* out, const void* in, long long n,
                           void* stream);

@@ -1654,7 +1654,10 @@ void launch_gemm_mxfp4_tile(void* out_bf16, const void* A, const void* W4,
 }
 
 // dynamic per-row fp8 quantization of bf16 activations:
-// a8[r][k] = round(a[r][k] / (amax_r / 448)); a_scale[r] = amax_r / 448
+// a8[r][k] = round(a[r][k] / (amax_r / 448)); a_scale[r] = amax_r / 448.
+// SWIZZLE: the pair-swizzled k order of the fp8 GEMMs; else natural order
+// (gemm_mxfp4_a8_tile_kernel)
+template <bool SWIZZLE>
 __global__ void quant_fp8_rows_kernel(unsigned char* __restrict__ a8,
                                       float* __restrict__ a_scale,
                                       const unsigned short* __restrict__ a,
@@ -1693,16 +1696,19 @@ __global__ void quant_fp8_rows_kernel(unsigned char* __restrict__ a8,
     // orig chunk i = s*32 + c*8 -> (s/2)*64 + c*16 + (s%2)*8
     const int s = i >> 5;
     const int c = (i >> 3) & 3;
-    const int dst = ((s >> 1) << 6) + (c << 4) + ((s & 1) << 3);
+    const int dst =
+        SWIZZLE ? ((s >> 1) << 6) + (c << 4) + ((s & 1) << 3) : i;
     *reinterpret_cast<uint64_t*>(outr + dst) =
         *reinterpret_cast<const uint64_t*>(q);
   }
 }
 
 void launch_quant_fp8_rows(void* a8, void* a_scale, const void* a, int rows,
-                           int cols, void* stream) {
+                           int cols, bool swizzle, void* stream) {
   int threads = cols >= 2048 ? 256 : 64;
-  hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(rows), dim3(threads), 0,
+  auto kern = swizzle ? quant_fp8_rows_kernel<true>
+                      : quant_fp8_rows_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(rows), dim3(threads), 0,
                      (hipStream_t)stream, (unsigned char*)a8,
                      (float*)a_scale, (const unsigned short*)a, cols);
 }

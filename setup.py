@@ -32,6 +32,7 @@ setup(
                 "mlrun_amd/ops/hip/kernels.hip",
                 "mlrun_amd/ops/hip/lora_sgmv.hip",
                 "mlrun_amd/ops/hip/gemm_fp8_tile.hip",
+                "mlrun_amd/ops/hip/gemm_mxfp4_a8_tile.hip",
                 "mlrun_amd/ops/hip/gemm_bf16_tile.hip",
                 "mlrun_amd/ops/hip/lm_head_logprobs.hip",
             ],
