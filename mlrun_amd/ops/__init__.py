@@ -923,22 +923,28 @@ def rope_kv_varlen(qkv: torch.Tensor, k_cache: torch.Tensor,
     """Packed-prefill rope(q,k) + KV append.  qkv [T, (hq+2*hkv)*d] is
     the packed projection buffer of several sequences; token t is roped
     in place at positions[t] and its k/v land in
-    cache[tok_slot[t], :, positions[t]].  bf16 caches only."""
+    cache[tok_slot[t], :, positions[t]].  bf16 caches only.
+
+    A token whose slot is outside [0, B) or whose position is outside
+    [0, min(Smax, len(cos_sin))) is skipped as a whole, on the GPU and
+    on the CPU alike: its qkv row is not roped and the caches are not
+    written."""
     T = qkv.shape[0]
     hkv, d = k_cache.shape[1], k_cache.shape[3]
     if qkv.is_cuda:
         _require_hip().rope_kv_varlen(qkv, k_cache, v_cache, positions,
                                       tok_slot, cos_sin, hq)
         return
-    q = qkv[:, :hq * d].view(T, hq, d)
-    k = qkv[:, hq * d:(hq + hkv) * d].view(T, hkv, d)
-    v = qkv[:, (hq + hkv) * d:(hq + 2 * hkv) * d].view(T, hkv, d)
-    rope_inplace(q, positions, cos_sin)
-    rope_inplace(k, positions, cos_sin)
-    for t in range(T):
-        slot, pos = int(tok_slot[t]), int(positions[t])
-        k_cache[slot, :, pos] = k[t]
-        v_cache[slot, :, pos] = v[t]
+    pos_l, slot_l = positions.long(), tok_slot.long()
+    limit = min(k_cache.shape[2], cos_sin.shape[0])
+    live = (pos_l >= 0) & (pos_l < limit) & (slot_l >= 0) & \
+        (slot_l < k_cache.shape[0])
+    pos_l, slot_l = pos_l[live], slot_l[live]
+    heads = qkv[live][:, :(hq + 2 * hkv) * d].reshape(-1, hq + 2 * hkv, d)
+    rope_inplace(heads[:, :hq + hkv], pos_l, cos_sin)
+    qkv[live, :(hq + 2 * hkv) * d] = heads.reshape(heads.shape[0], -1)
+    k_cache[slot_l, :, pos_l] = heads[:, hq:hq + hkv]
+    v_cache[slot_l, :, pos_l] = heads[:, hq + hkv:]
 
 
 def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor,
@@ -954,7 +960,12 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor,
     cache[slots[i], h // G] — the chunk's own k/v must already be in
     the cache (rope_kv_varlen).  Returns out [T, Hq*D] bf16.
     max_q_len (the longest chunk) sizes the GPU grid; pass it from the
-    host-side lengths to avoid a device sync."""
+    host-side lengths to avoid a device sync.
+
+    A sequence whose slot is outside [0, B), whose kv_start is negative
+    or whose first row is negative is skipped, on the GPU and on the CPU
+    alike: its rows of `out` are left as they are.  Rows past T are not
+    computed, and no key at or past Smax is read."""
     T, Hq, D = q.shape
     Hkv = k_cache.shape[1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -976,7 +987,9 @@ def attn_prefill(q: torch.Tensor, k_cache: torch.Tensor,
     out_v = out.view(T, Hq, D)
     for i in range(len(cu) - 1):
         slot, start = int(slots[i]), int(kv_start[i])
-        for j in range(cu[i + 1] - cu[i]):
+        if not 0 <= slot < k_cache.shape[0] or start < 0 or cu[i] < 0:
+            continue
+        for j in range(min(cu[i + 1], T) - cu[i]):
             row = cu[i] + j
             length = start + j + 1
             for h in range(Hq):
@@ -1105,7 +1118,9 @@ def attn_verify(q: torch.Tensor, k_cache: torch.Tensor,
     cached BEFORE these QL tokens.  Query j of row b sits at position
     base_lens[b] + j and attends to rows 0..base_lens[b]+j of
     cache[b, h // G]; the QL new k/v rows must already be in the cache
-    (rope_kv_varlen).  Returns out [B*QL, Hq*D] bf16.
+    (rope_kv_varlen).  Returns out [B*QL, Hq*D] bf16.  A row with
+    base_lens[b] < 0 or base_lens[b] + QL > Smax is skipped, on the GPU
+    and on the CPU alike: its QL rows of `out` are left as they are.
 
     D = 128, G <= 8, 1 <= QL <= 8, bf16 caches — anything else raises
     ValueError.  On GPU one workgroup serves a whole KV head (K/V read
@@ -1147,9 +1162,12 @@ def attn_verify(q: torch.Tensor, k_cache: torch.Tensor,
                         partial_ws, nsplit)
         return out
     # fp32 reference: the attn_prefill reference with every sequence a
-    # chunk of QL rows on its own cache row
+    # chunk of QL rows on its own cache row; a row the kernel skips
+    # goes there as slot -1, which that reference skips
     cu = torch.arange(B + 1, dtype=torch.int32) * QL
     slots = torch.arange(B, dtype=torch.int32)
+    base = base_lens.to(torch.int64).cpu()
+    slots[(base < 0) | (base + QL > Smax)] = -1
     return attn_prefill(q.reshape(B * QL, Hq, D), k_cache, v_cache, cu,
                         slots, base_lens, scale, out=out)
 

@@ -42,6 +42,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import decode_refs as R  # noqa: E402
 from decode_refs import f64  # noqa: E402
+from gpu_fence import Fenced  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,38 +50,6 @@ requires_gpu = pytest.mark.skipif(not torch.cuda.is_available(),
                                   reason="needs MI355X")
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PAD = 64        # fence elements on either side: keeps 16-byte alignment
-
-
-class Fenced:
-    """`values` (or NaN of that shape and dtype) on the GPU inside a
-    flat buffer that is NaN (0x7F) everywhere else: PAD elements on both
-    sides, and `spare` elements of NaN capacity behind the values that
-    belong to `.all` but not to `.t`."""
-
-    def __init__(self, values=None, shape=None, dtype=None, spare=0):
-        if values is None:
-            values = torch.full(shape, self.poison(dtype), dtype=dtype)
-        n = values.numel()
-        flat = torch.full((PAD + n + spare + PAD,),
-                          self.poison(values.dtype), dtype=values.dtype)
-        flat[PAD:PAD + n] = values.reshape(-1)
-        self.buf = flat.cuda()
-        self.n, self.spare = n, spare
-        self.t = self.buf[PAD:PAD + n].view(values.shape)
-        self.all = self.buf[PAD:PAD + n + spare]
-        assert self.t.is_contiguous() and self.t.data_ptr() % 16 == 0
-
-    @staticmethod
-    def poison(dtype):
-        return 0x7F if dtype == torch.uint8 else float("nan")
-
-    def intact(self):
-        """Nothing wrote outside the values."""
-        outside = torch.cat([self.buf[:PAD], self.buf[PAD + self.n:]])
-        if outside.dtype == torch.uint8:
-            return bool((outside == 0x7F).all())
-        return bool(torch.isnan(outside).all())
 
 
 def _ext():
